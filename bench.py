@@ -15,11 +15,16 @@ collective, an RCCL all-gather of the converged (X, U, J, status, n_bwd, n_fwd) 
 on a side stream while the rest of the job still solves (dpilqr_amd/sharding.py ResultBuffers; buffers pre-allocated
 and the collective warmed on them outside the clock).
 
-The timed K-step job is REPEATED on disjoint seeds inside one invocation -- --reps times if given, otherwise five times and on
-until the repetitions add up to --min-seconds (2 s) of timed work, at most --max-reps (48) -- and `value` / `ms_per_step` are the
-MEDIAN repetition (max over ranks each); the spread is reported beside them (`repetitions`).
+By default exactly K steps are timed, once.  The K-step job can be REPEATED on disjoint seeds inside one invocation -- --reps
+times, or on until the repetitions add up to --min-seconds of timed work, at most --max-reps -- and `value` / `ms_per_step` are
+then the MEDIAN repetition (max over ranks each); the spread is reported beside them (`repetitions`).
 
-    python bench.py [--gpus N --steps K --warmup W]          (N > 1 without a launcher: starts its own N ranks)
+A plain run does only what the headline needs: set-up, W warm-up steps, the timed steps, the result line.  --full adds what
+else the benchmark measures, after and outside the timed region (per-kernel events in the timed run, the rooflines, the single
+1024-item batch, the CPU baselines and the live parity check against the oracle, the `configs` block).  --dump-outputs DIR
+writes what the timed path returned for the last step of the last repetition (rank 0's items) as DIR/<name>.npy in float64.
+
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]   (N > 1 without a launcher: starts its own N ranks)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 A rank count that is not --gpus, or fewer visible GPUs than ranks (RCCL), ends the run with a non-zero exit code.
 
@@ -330,6 +335,26 @@ def cfg5_config(cpu=True, n_lqr_iter=8):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, r):
+    """--dump-outputs: the last timed step's results, what ProblemBatch.solve returns for its items (X, U, J, status, n_bwd,
+    n_fwd), as out_dir/<name>.npy in float64 (the integers exactly) -- two builds run with the same arguments solve the same
+    seeds and can be compared output for output.  Above 64 MB in all (a --batch far beyond cfg2's 1024) a fixed, seeded sample
+    of the items is written, their indices beside them as items.npy."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {k: v.cpu().numpy().astype(np.float64) for k, v in r.items()}
+    n = len(arrays["J"])
+    per_item = sum(a.nbytes for a in arrays.values()) // n
+    if n * per_item > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, DUMP_LIMIT_BYTES // (per_item + 8), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays["items"] = keep.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(out_dir / f"{k}.npy", a)
+
+
 def _read(path):
     try:
         return Path(path).read_text().strip()
@@ -416,10 +441,9 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=None, help="repetitions of the timed K-step job (disjoint seeds); the median is reported.  "
-                    "Given: exactly that many.  Not given: five, and more while --min-seconds is not reached")
-    ap.add_argument("--min-seconds", type=float, default=2.0, help="keep repeating the timed job (beyond --reps, on further disjoint seeds, at "
-                    "most --max-reps times) until the repetitions add up to this much timed work: a 20-step job is 25 ms, and five of "
-                    "them are neither a stable median nor visible to a once-per-second utilisation sampler")
+                    "Given: exactly that many.  Not given: one, and more while --min-seconds is not reached")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="keep repeating the timed job (beyond --reps, on further disjoint seeds, at "
+                    "most --max-reps times) until the repetitions add up to this much timed work (default 0: --steps steps are timed, once)")
     ap.add_argument("--max-reps", type=int, default=48)
     ap.add_argument("--batch", type=int, default=1024, help="sub-problems per GPU per step (cfg2: 1024)")
     ap.add_argument("--window", type=int, default=6144, help="sub-problems in flight per GPU (a multiple of 3072 = three sweep wavefronts per SIMD)")
@@ -431,6 +455,10 @@ def main():
                     "(per-kernel breakdown; costs ~4 %% of throughput in dispatch gaps) instead of the Riccati sweep only")
     ap.add_argument("--cpu-sample", type=int, default=16384)
     ap.add_argument("--no-configs", action="store_true", help="skip the `configs` block (cfg3 / cfg4 / cfg5 after the headline; N = 1 only)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: per-kernel events in the timed run, rooflines, the single "
+                    "batch, CPU baselines and parity (unless --no-cpu-baseline), the `configs` block (unless --no-configs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's results (rank 0's items) as "
+                    "DIR/<name>.npy in float64")
     args = ap.parse_args()
 
     if args.gpus < 1:
@@ -469,7 +497,7 @@ def main():
     from dpilqr_amd.sharding import ResultBuffers
     _lib.require_gpu()
 
-    B, reps = args.batch, max(1, args.reps if args.reps is not None else 5)
+    B, reps = args.batch, max(1, args.reps if args.reps is not None else 1)
     max_reps = max(reps, args.max_reps) if (args.reps is None and args.min_seconds > 0) else reps
     Q, R, Qf = np.diag([1.0, 1, 0, 0]), np.eye(2), 1000.0 * np.eye(4)
 
@@ -487,7 +515,7 @@ def main():
     seed_base = rank * seeds_per_rank                                    # weak scaling: every rank its own seeds
     # repetition r's job is generated just before it runs, outside the clock (only repetition 0's stays: the parity and roofline
     # legs look at it)
-    job_of = lambda r: make_job(args.steps, seed_base + r * args.steps * B, host=(r == 0 and rank == 0))
+    job_of = lambda r: make_job(args.steps, seed_base + r * args.steps * B, host=(r == 0 and rank == 0 and args.full))
     jobs = [job_of(0)]
     warm = make_job(args.warmup, seed_base + max_reps * args.steps * B) if args.warmup > 0 else None
     # N > 1: the results' home and the gathered results of all ranks, allocated once for the job's shape
@@ -516,12 +544,14 @@ def main():
         run(warm, None)                 # W untimed steps: every kernel variant loaded, workspace pool filled
     if rb is not None:
         rb.warm()                       # the collective on the timed job's own buffers and message sizes, outside the clock
-    _lib.profile_enable(True, classes=None if args.profile_all else ["riccati"]); _lib.profile_read(reset=True)
-    for w in (12, 8, 4):
-        _lib.profile_read_sweep(w, reset=True)
+    if args.full:                       # event pairs around the sweep's launches: the roofline's kernel time
+        _lib.profile_enable(True, classes=None if args.profile_all else ["riccati"]); _lib.profile_read(reset=True)
+        for w in (12, 8, 4):
+            _lib.profile_read_sweep(w, reset=True)
     times = []
     own_times = []                      # this rank's own clock around the same region (per-rank values of the JSON line)
     r0 = None
+    last = None                         # --dump-outputs: the last step's items of the latest repetition
     rep = 0
     while True:
         job = jobs[0] if rep == 0 else job_of(rep)
@@ -551,6 +581,8 @@ def main():
                 g = rb.results()    # and every rank's block is a finished job (status 1..3 everywhere)
                 assert torch.equal(g["X"][rank], r["X"]) and torch.equal(g["J"][rank], r["J"]), "all-gather returned another block"
                 assert bool(((g["status"] >= 1) & (g["status"] <= 3)).all()), "a rank's gathered results are not finished solves"
+        if args.dump_outputs:           # (a copy: with N > 1 the results live in buffers the next repetition overwrites)
+            last = {k: v[-B:].clone() for k, v in r.items()}
         del r
         if rep > 0:
             del job
@@ -559,9 +591,12 @@ def main():
         if rep >= max_reps or (rep >= reps and sum(times) >= args.min_seconds):
             break
     reps = rep
-    prof = _lib.profile_read(reset=True)
-    sweep_variants = {w: _lib.profile_read_sweep(w, reset=True) for w in (12, 8, 4)}
-    _lib.profile_enable(False)
+    if args.full:
+        prof = _lib.profile_read(reset=True)
+        sweep_variants = {w: _lib.profile_read_sweep(w, reset=True) for w in (12, 8, 4)}
+        _lib.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), last)
 
     order = sorted(range(reps), key=lambda i: times[i])
     elapsed = times[order[(reps - 1) // 2]] if reps % 2 else 0.5 * (times[order[reps // 2 - 1]] + times[order[reps // 2]])
@@ -594,6 +629,28 @@ def main():
                 raise SystemExit(f"bench.py: {world} ranks but their devices are not pairwise distinct: {ident}")
 
     if rank == 0:
+        nb = r0["n_bwd"].cpu().numpy(); nf = r0["n_fwd"].cpu().numpy(); st = r0["status"].cpu().numpy()
+        out = {
+            "metric": "ilqr_subproblems_per_sec", "value": value, "unit": "subproblems/s", "n_gpus": world,
+            "ranks_seen": ranks_seen, "backend": (backend if world > 1 else None),
+            "ranks": ranks,          # per rank: device index / PCI bus / uuid as the runtime reports them, its own value
+            "n1_path": ("plain" if rb is None else "gather-path (diagnostic)") if world == 1 else None,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "repetitions": {"n": reps, "statistic": "median", "ms_per_step": [t / args.steps * 1e3 for t in times],
+                            "value_min_max": [total_units / max(times), total_units / min(times)]},
+            "config": {"workload": f"cfg2: batches of {B} independent 5-agent DoubleIntDynamics4D iLQR sub-problems per GPU "
+                                   "per step, T=50, scripts/analysis.py scenario distribution, tol=1e-3, n_lqr_iter=50; "
+                                   f"{args.steps} steps = {args.steps * B} distinct seeds per GPU, window of {args.window} in flight; "
+                                   f"{reps} repetition(s) of the job on disjoint seeds, the median is reported",
+                       "batch_per_gpu": B, "window": args.window, "n_x": N_X, "n_u": N_U, "horizon": T,
+                       "mean_backward_passes": float(nb.mean()), "mean_forward_passes": float(nf.mean()),
+                       "converged_frac": float((st == 1).mean()), "linesearch_failed_frac": float((st == 2).mean()),
+                       "parallelism": (f"batch-sharded x{world}, one all-gather in chunks of {args.gather_chunk} items overlapped with the solve"
+                                       if world > 1 else "single GPU")},
+            "gather_timeline": gather_marks.get("timeline"),
+        }
+    if rank == 0 and args.full:
         # roofline = the dominant kernel: the sweep variant (wavefronts per workgroup) that ran the full-window launches,
         # exactly the launches a rocprofv3 kernel trace lists under that instantiation's name; the job's other sweep
         # launches (the draining tail's smaller variants) are reported beside it under "all_sweep_launches"
@@ -701,29 +758,8 @@ def main():
                   "subproblems_per_s": B / float(np.median(t1)), "global_iterations": int(r1["n_bwd"].max().item()),
                   "note": "one 1024-item batch solved alone (median of 5): bounded by the batch's longest item, "
                           "max(n_bwd) dependent iterations of one sweep + one line search each"}
-        nb = r0["n_bwd"].cpu().numpy(); nf = r0["n_fwd"].cpu().numpy(); st = r0["status"].cpu().numpy()
-        out = {
-            "metric": "ilqr_subproblems_per_sec", "value": value, "unit": "subproblems/s", "n_gpus": world,
-            "ranks_seen": ranks_seen, "backend": (backend if world > 1 else None),
-            "ranks": ranks,          # per rank: device index / PCI bus / uuid as the runtime reports them, its own value
-            "n1_path": ("plain" if rb is None else "gather-path (diagnostic)") if world == 1 else None,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "repetitions": {"n": reps, "statistic": "median", "ms_per_step": [t / args.steps * 1e3 for t in times],
-                            "value_min_max": [total_units / max(times), total_units / min(times)]},
-            "config": {"workload": f"cfg2: batches of {B} independent 5-agent DoubleIntDynamics4D iLQR sub-problems per GPU "
-                                   "per step, T=50, scripts/analysis.py scenario distribution, tol=1e-3, n_lqr_iter=50; "
-                                   f"{args.steps} steps = {args.steps * B} distinct seeds per GPU, window of {args.window} in flight; "
-                                   f"the job is repeated {reps} times on disjoint seeds and the median is reported",
-                       "batch_per_gpu": B, "window": args.window, "n_x": N_X, "n_u": N_U, "horizon": T,
-                       "mean_backward_passes": float(nb.mean()), "mean_forward_passes": float(nf.mean()),
-                       "converged_frac": float((st == 1).mean()), "linesearch_failed_frac": float((st == 2).mean()),
-                       "parallelism": (f"batch-sharded x{world}, one all-gather in chunks of {args.gather_chunk} items overlapped with the solve"
-                                       if world > 1 else "single GPU")},
-            "gather_timeline": gather_marks.get("timeline"),
-            "roofline": roofline, "roofline_tiles_through_hbm": tiled, "single_batch_1024": single,
-            "kernel_ms_per_step": {k: v["ms"] / (args.steps * reps) for k, v in prof.items() if v["launches"]},
-        }
+        out.update(roofline=roofline, roofline_tiles_through_hbm=tiled, single_batch_1024=single,
+                   kernel_ms_per_step={k: v["ms"] / (args.steps * reps) for k, v in prof.items() if v["launches"]})
         if world == 1 and not args.no_cpu_baseline:
             x0_h, xf_h = j0["x0_h"], j0["xf_h"]
             ns = min(args.cpu_sample, x0_h.shape[0])
@@ -760,6 +796,7 @@ def main():
             out["configs"] = {"cfg2_single_batch": dict(single, workload="configs[1] read literally: one batch of 1024 sub-problems alone"),
                               "cfg3": scenario_config("cfg3", cpu=cpu_legs), "cfg4": scenario_config("cfg4", cpu=cpu_legs),
                               "cfg5": cfg5_config(cpu=cpu_legs)}
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -18,7 +18,7 @@ echo "== phase stamps, fused sweep, 1024 and 6144 items"
 python scripts/phase_stamps.py 1024 --fused 2>&1 | q
 python scripts/phase_stamps.py 6144 --fused 2>&1 | q
 echo "== FMA contraction library-wide (fma) vs main: bench, 20 steps"
-for lib in "" $V/libdpilqr_hip_fma.so; do echo "DPILQR_LIB=$lib"; DPILQR_LIB=$lib python bench.py --steps 20 --no-cpu-baseline 2>/dev/null | python scripts/benchline.py; done
+for lib in "" $V/libdpilqr_hip_fma.so; do echo "DPILQR_LIB=$lib"; DPILQR_LIB=$lib python bench.py --steps 20 --full --no-cpu-baseline 2>/dev/null | python scripts/benchline.py; done
 } > $out/ab.txt 2>&1
 DPILQR_LIB=$V/libdpilqr_hip_fma.so python -m pytest tests -m gpu -q -k "not cfg4 and not cfg5 and not bench" > $out/pytest_fma.log 2>&1
 {

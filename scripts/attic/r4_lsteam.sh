@@ -12,7 +12,7 @@ for t in 0 1; do
   echo "== DPILQR_LS_NO_TEAM=$t" >> $out/lsteam.txt
   timeout 300 python scripts/bench_ls.py --iters 8 --B 1024 2>&1 | q >> $out/lsteam.txt
   timeout 300 python scripts/bench_ls.py --iters 8 --B 256 2>&1 | q >> $out/lsteam.txt
-  timeout 600 python bench.py --steps 20 --no-cpu-baseline --profile-all 2>/dev/null | python -c "
+  timeout 600 python bench.py --steps 20 --full --no-cpu-baseline --profile-all 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(round(d['value']), 'sub/s', 'single_batch ms', round(d['single_batch_1024']['ms'],3), {k: round(v,4) for k,v in d['kernel_ms_per_step'].items()})" >> $out/lsteam.txt

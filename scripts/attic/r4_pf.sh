@@ -16,7 +16,7 @@ done; done
 for t in default "$@" default "$@"; do
   if [ $t != default ]; then export DPILQR_LIB=$PWD/dpilqr_amd/variants/libdpilqr_hip_$t.so; else unset DPILQR_LIB; fi
   echo "== $t"
-  timeout 600 python bench.py --steps 20 --no-cpu-baseline --profile-all 2>/dev/null | python -c "
+  timeout 600 python bench.py --steps 20 --full --no-cpu-baseline --profile-all 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(round(d['value']), 'sub/s', 'single_batch ms', round(d['single_batch_1024']['ms'],3), {k: round(v,4) for k,v in d['kernel_ms_per_step'].items()})"

@@ -12,7 +12,7 @@ done; done
 for t in 0 1; do
   if [ $t == 1 ]; then export DPILQR_NO_TEAM=1; else unset DPILQR_NO_TEAM; fi
   echo "DPILQR_NO_TEAM=$t"
-  timeout 600 python bench.py --steps 20 --no-cpu-baseline 2>/dev/null | python -c "
+  timeout 600 python bench.py --steps 20 --full --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(round(d['value']), 'sub/s', 'single_batch ms', round(d['single_batch_1024']['ms'],3), 'tiled ms', round(d['roofline_tiles_through_hbm']['launch_ms'],4), 'read_only frac', round(d['roofline_tiles_through_hbm']['read_only']['frac'],4))"

@@ -14,6 +14,7 @@ only ever read the .npz files.
 
 Manifest:
   g1_models.npz      f / integrate / linearize for Model 0..7
+  g1r_models_compiled_ref.npz  integrate / linearize for Model 0..7 on G1's inputs and a wider seeded sample
   g2_costs.npz       ReferenceCost, quadraticize_distance, ProximityCost, GameCost
   g3_passes_*.npz    rollout, backward pass (K,d), forward pass (10 alphas)
   g4_solves_*.npz    full ilqrSolver.solve incl. decision trace
@@ -140,6 +141,33 @@ def g1_models():
         x = m(x, u); traj.append(x.copy())
     out["DoubleInt4D_reftest_traj"] = np.array(traj)
     np.savez_compressed(OUT / "g1_models.npz", **out)
+
+
+def g1r_models():
+    """integrate / linearize of the reference's compiled models (bbdynamics.cpp) on G1's inputs followed by a wider seeded
+    sample (states up to four times G1's scale): what tests/test_oracle_golden.py holds the oracle to, bit for bit against
+    oracle/_ref wherever that is built."""
+    g1 = np.load(OUT / "g1_models.npz")
+    out = {}
+    rng = np.random.default_rng(1002)
+    for name, cls in MODEL_CLASSES:
+        n_s, n_c = cls(0.1).n_x, cls(0.1).n_u
+        n = 56
+        x = rng.normal(size=(n, n_s)) * np.where(np.arange(n) % 2 == 0, 1.0, 4.0)[:, None]
+        u = rng.normal(size=(n, n_c)) * 0.5
+        if name == "Quadcopter12D":
+            x[:, 3:6] = rng.uniform(-1.2, 1.2, size=(n, 3))   # Euler angles, away from cos(theta)=0
+            u[:, :3] *= 1e-3
+        dt = np.where(np.arange(n) % 2 == 0, 0.05, 0.1)
+        x = np.concatenate([g1[f"{name}_x"], x]); u = np.concatenate([g1[f"{name}_u"], u]); dt = np.concatenate([g1[f"{name}_dt"], dt])
+        xn = np.zeros_like(x); A = np.zeros((len(x), n_s, n_s)); B = np.zeros((len(x), n_s, n_c))
+        for i in range(len(x)):
+            m = cls(float(dt[i]))
+            xn[i] = m(x[i].copy(), u[i].copy())
+            A[i], B[i] = m.linearize(x[i].copy(), u[i].copy())
+        out.update({f"{name}_x": x, f"{name}_u": u, f"{name}_dt": dt, f"{name}_xn": xn, f"{name}_A": A, f"{name}_B": B,
+                    f"{name}_n_g1": np.array(len(g1[f"{name}_x"]))})
+    np.savez_compressed(OUT / "g1r_models_compiled_ref.npz", **out)
 
 
 # --------------------------------------------------------------------------- G2
@@ -754,10 +782,10 @@ def g10_harness():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8"]
+    which = sys.argv[1:] or ["g1", "g1r", "g2", "g3", "g4", "g5", "g6", "g7", "g8"]
     for w in which:
         print("generating", w, flush=True)
-        {"g1": g1_models, "g2": g2_costs, "g3": g3_passes, "g4": g4_solves,
+        {"g1": g1_models, "g1r": g1r_models, "g2": g2_costs, "g3": g3_passes, "g4": g4_solves,
          "g5": g5_dispatch, "g6": g6_scenarios, "g7": g7_callers, "g8": g8_hetero, "g9": g9_chaos, "g10": g10_harness}[w]()
     for f in sorted(OUT.glob("*.npz")):
         print(f"{f.name:40s} {f.stat().st_size/1024:8.1f} KiB")

@@ -635,8 +635,8 @@ def test_plain_bench_gpus_2_starts_two_ranks_itself():
     starts its own two ranks before anything touches the GPU and rank 0's line says n_gpus = 2 (gloo, both ranks on the one GPU
     of this box: the multi-rank path as a diagnostic)."""
     import json
-    out = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--reps", "2", "--gather-chunk", "512", "--no-cpu-baseline"],
-                     {"DPILQR_BENCH_BACKEND": "gloo"})
+    out = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--reps", "2", "--gather-chunk", "512", "--no-cpu-baseline",
+                      "--full"], {"DPILQR_BENCH_BACKEND": "gloo"})
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, "exactly one JSON line (rank 0's)"
@@ -649,6 +649,32 @@ def test_plain_bench_gpus_2_starts_two_ranks_itself():
     assert all(r["value"] > 0 and r["device_name"] and r["pci_bus"] for r in d["ranks"])
     assert d["value"] <= sum(r["value"] for r in d["ranks"]) * 1.0001        # MAX over ranks bounds the job's time
     assert "batch-sharded x2" in d["config"]["parallelism"]
+
+
+def test_plain_bench_times_its_steps_once_and_dumps_the_last_step(dp, tmp_path):
+    """A plain `bench.py` line: --steps steps timed once, none of the --full legs; --dump-outputs writes the last step's items
+    (seeds (K-1)*B .. K*B-1 of rank 0) as float64 arrays, equal to a solve of those seeds on their own (the window's schedule
+    does not change an item's arithmetic)."""
+    import json
+    import torch
+    from dpilqr_amd.util import random_setup_batch
+    K, B = 2, 256
+    out = _run_bench(["--gpus", "1", "--steps", str(K), "--warmup", "1", "--batch", str(B), "--dump-outputs", str(tmp_path)], {},
+                     timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == K and d["repetitions"]["n"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["metric"] == "ilqr_subproblems_per_sec" and d["unit"] == "subproblems/s" and d["dtype"] == "f64" and d["higher_is_better"]
+    assert not {"roofline", "cpu_baseline", "configs", "single_batch_1024"} & set(d)
+    x0, xf = random_setup_batch(((K - 1) * B, B), 5, 4, var=2.5, n_d=2, energy=10.0)
+    pb = dp.ProblemBatch([0] * 5, [2] * 5, xf, np.diag([1.0, 1, 0, 0]), np.eye(2), 1000.0 * np.eye(4), 0.5, 0.1, 50)
+    r = pb.solve(x0, torch.zeros((B, 50, 10), dtype=torch.float64, device="cuda"), n_lqr_iter=50, tol=1e-3)
+    for k in ("X", "U", "J", "status", "n_bwd", "n_fwd"):
+        a = np.load(tmp_path / f"{k}.npy")
+        assert a.dtype == np.float64 and a.shape == tuple(r[k].shape), k
+        np.testing.assert_array_equal(a, r[k].cpu().numpy().astype(np.float64), err_msg=k)
 
 
 def test_plain_bench_gpus_2_on_one_gpu_over_rccl_fails_loudly():

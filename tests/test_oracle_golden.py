@@ -29,16 +29,23 @@ def test_models_vs_reference(golden, name):
 
 @pytest.mark.parametrize("name", MODEL_NAMES)
 def test_models_vs_compiled_reference(golden, name):
-    """oracle/_ref = the reference's own bbdynamics.cpp compiled where it lies."""
-    if orc.ref_lib() is None:
-        pytest.skip("oracle/_ref not built (reference not mounted)")
-    z = golden("g1_models"); m = int(z[f"{name}_enum"])
+    """The reference's own bbdynamics.cpp compiled: its outputs on G1's inputs and on a wider seeded sample are recorded in
+    g1r_models_compiled_ref (make_golden.py g1r); on G1's inputs they are G1's bit for bit.  oracle/_ref = the same source
+    compiled beside the oracle where the reference lies: where it is built, it reproduces the record bit for bit."""
+    z, g1 = golden("g1r_models_compiled_ref"), golden("g1_models")
+    m, n1 = int(g1[f"{name}_enum"]), int(z[f"{name}_n_g1"])
+    for k in ("x", "u", "dt", "xn", "A", "B"):
+        np.testing.assert_array_equal(z[f"{name}_{k}"][:n1], g1[f"{name}_{k}"])
+    ref = orc.ref_lib() is not None
     for i in range(z[f"{name}_x"].shape[0]):
         x, u, dt = z[f"{name}_x"][i], z[f"{name}_u"][i], float(z[f"{name}_dt"][i])
-        np.testing.assert_array_equal(orc.model_integrate(m, x, u, dt, ref=True), z[f"{name}_xn"][i])
-        A, B = orc.model_linearize(m, x, u, dt, ref=True)
-        np.testing.assert_array_equal(A, z[f"{name}_A"][i]); np.testing.assert_array_equal(B, z[f"{name}_B"][i])
-        assert relerr(orc.model_integrate(m, x, u, dt), orc.model_integrate(m, x, u, dt, ref=True)) < 1e-13
+        if ref:
+            np.testing.assert_array_equal(orc.model_integrate(m, x, u, dt, ref=True), z[f"{name}_xn"][i])
+            A, B = orc.model_linearize(m, x, u, dt, ref=True)
+            np.testing.assert_array_equal(A, z[f"{name}_A"][i]); np.testing.assert_array_equal(B, z[f"{name}_B"][i])
+        assert relerr(orc.model_integrate(m, x, u, dt), z[f"{name}_xn"][i]) < 1e-13
+        A, B = orc.model_linearize(m, x, u, dt)
+        assert relerr(A, z[f"{name}_A"][i]) < 1e-14 and relerr(B, z[f"{name}_B"][i]) < 1e-14
 
 
 def test_reference_own_double_int_test(golden):
