@@ -25,11 +25,13 @@ class Model(Enum):
     HumanLin6D = 6
     Quadcopter12D = 7
     HumanPad12D = 8      # this library's own: HumanDynamics6D zero-padded to 12 states / 4 controls (dpilqr_hip.h)
+    # (9 is not assigned)
+    Bike5D = 10          # BikeDynamics5D (dynamics.py:253-278): a SymbolicModel in the reference, a device model here
 
 
 MODEL_DIMS = {Model.DoubleInt4D: (4, 2), Model.DoubleInt6D: (6, 3), Model.Car3D: (3, 2), Model.Unicycle4D: (4, 2),
               Model.Quadcopter6D: (6, 3), Model.Human6D: (6, 3), Model.HumanLin6D: (6, 3), Model.Quadcopter12D: (12, 4),
-              Model.HumanPad12D: (12, 4)}
+              Model.HumanPad12D: (12, 4), Model.Bike5D: (5, 2)}
 
 
 def _check(model, x, u):
@@ -65,7 +67,8 @@ def f(x, u, model):
 
 
 def integrate(x, u, dt, model):
-    """One zero-order-hold step: classical RK4 with 5 sub-steps (pyx:93-123, bbdynamics.cpp:39-93)."""
+    """One zero-order-hold step: classical RK4 with 5 sub-steps (pyx:93-123, bbdynamics.cpp:39-93); Model.Bike5D takes ONE
+    RK4 step of dt, as the reference's DynamicalModel.__call__ does for it (dynamics.py:18-38, :73-78)."""
     return _run("integrate", model, x, u, dt)
 
 

@@ -29,7 +29,7 @@ def _family_model(n_s, n_c):
         if dims == (n_s, n_c):
             return tag
     raise ValueError(f"no device model family with (n_x, n_u) = ({n_s}, {n_c}) per agent; "
-                     "supported: (3,2), (4,2), (6,3), (12,4)")
+                     "supported: (3,2), (4,2), (5,2), (6,3), (12,4)")
 
 
 def _point_batch(game, x, terminal):

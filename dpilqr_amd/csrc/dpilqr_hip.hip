@@ -58,17 +58,34 @@ namespace {
 
 constexpr int kMaxAgents = 64;
 
-int family_nc(int ns) { return ns == 3 ? 2 : ns == 4 ? 2 : ns == 6 ? 3 : ns == 12 ? 4 : -1; }
+int family_nc(int ns) { return ns == 3 ? 2 : ns == 4 ? 2 : ns == 5 ? 2 : ns == 6 ? 3 : ns == 12 ? 4 : -1; }
+
+// The five-state family (BikeDynamics5D) is served up to n_x = 60 (twelve bikes) and in fp64 only: the large-cluster path
+// (tu_big.hip) and the fp32 arm have no instantiation for it.
+int32_t check_family5(const dpilqr_batch_desc* d, bool f32) {
+    if (d->n_s != 5) return DPILQR_OK;
+    if (f32) return fail(DPILQR_EUNSUPPORTED, "the fp32 arm does not serve the five-state family (BikeDynamics5D)");
+    if (d->k * d->n_s > 60)
+        return fail(DPILQR_EUNSUPPORTED, "k=%d BikeDynamics5D agents (n_x=%d): the five-state family is served up to 12 agents (n_x <= 60)",
+                    d->k, d->k * d->n_s);
+    return DPILQR_OK;
+}
 
 int32_t check_desc(const dpilqr_batch_desc* d) {
     if (!d) return fail(DPILQR_EINVAL, "desc is NULL");
     if (d->B < 0 || d->k < 1 || d->T < 1) return fail(DPILQR_EINVAL, "bad sizes B=%d k=%d T=%d", d->B, d->k, d->T);
     if (d->k > kMaxAgents) return fail(DPILQR_EUNSUPPORTED, "k=%d agents per sub-problem exceeds %d", d->k, kMaxAgents);
     if (family_nc(d->n_s) != d->n_c)
-        return fail(DPILQR_EINVAL, "(n_s,n_c)=(%d,%d) is not a model family; expected (3,2),(4,2),(6,3),(12,4)", d->n_s, d->n_c);
+        return fail(DPILQR_EINVAL, "(n_s,n_c)=(%d,%d) is not a model family; expected (3,2),(4,2),(5,2),(6,3),(12,4)", d->n_s, d->n_c);
     if (d->B > 0 && (!d->model || !d->n_dims || !d->xf || !d->Q || !d->R || !d->Qf || !d->radius))   // an empty batch owns nothing
         return fail(DPILQR_EINVAL, "desc holds a NULL device pointer");
-    return DPILQR_OK;
+    // ... and each aligned to its element type: a kernel reading a misaligned one faults the device
+    const uintptr_t ints = reinterpret_cast<uintptr_t>(d->model) | reinterpret_cast<uintptr_t>(d->n_dims);
+    const uintptr_t dbls = reinterpret_cast<uintptr_t>(d->xf) | reinterpret_cast<uintptr_t>(d->Q) | reinterpret_cast<uintptr_t>(d->R) |
+                           reinterpret_cast<uintptr_t>(d->Qf) | reinterpret_cast<uintptr_t>(d->radius);
+    if (d->B > 0 && (ints % alignof(int32_t) != 0 || dbls % alignof(double) != 0))
+        return fail(DPILQR_EINVAL, "desc holds a device pointer that is not aligned to its element type");
+    return check_family5(d, false);
 }
 
 hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
@@ -358,6 +375,7 @@ int32_t solve_impl(dpilqr_solver* solver, const dpilqr_batch_desc* desc, const R
                    int32_t* n_bwd, int32_t* n_fwd, double* trace, R* K_out, R* d_out, int32_t n_global_iter,
                    int32_t resume, hipStream_t st) {
     int32_t rc = check_desc(desc);
+    if (!rc) rc = check_family5(desc, sizeof(R) == 4);
     if (rc) return rc;
     if (desc->B == 0) return DPILQR_OK;   // an empty batch: nothing to read or write
     if (!x0 || !U || !X || !J || !status || !n_bwd || !n_fwd || !workspace)
@@ -580,7 +598,7 @@ int32_t dpilqr_device_info(int32_t dev, int32_t* n_cu, int32_t* lds_bytes, char*
 }
 
 int32_t dpilqr_model_dims(int32_t model, int32_t* n_s, int32_t* n_c) {
-    if (model < 0 || model >= kNumModels || !n_s || !n_c) return fail(DPILQR_EINVAL, "unknown model %d", model);
+    if (model < 0 || model >= kNumModels || model_ns(model) < 0 || !n_s || !n_c) return fail(DPILQR_EINVAL, "unknown model %d", model);
     *n_s = model_ns(model);
     *n_c = model_nc(model);
     return DPILQR_OK;
@@ -698,7 +716,7 @@ int32_t dpilqr_backward_pass_fused(const dpilqr_batch_desc* desc, const double* 
     if (desc->B == 0) return DPILQR_OK;
     if (!X || !U || !mu || !K || !d) return fail(DPILQR_EINVAL, "backward_pass_fused: NULL pointer");
     if (!fused_sweep_applies(*desc))
-        return fail(DPILQR_EUNSUPPORTED, "backward_pass_fused: needs 6..15 four-state, 1..10 six-state or 1..6 CarDynamics3D agents, or at most five "
+        return fail(DPILQR_EUNSUPPORTED, "backward_pass_fused: needs 6..15 four-state, 1..10 six-state, 1..6 CarDynamics3D or 1..4 BikeDynamics5D agents, or at most five "
                                          "DoubleIntDynamics4D / UnicycleDynamics4D agents with n_dims = 2 (uniform_model hints)");
     rc = launch_riccati_fused(*desc, X, U, mu, K, d, singular, nullptr, nullptr, desc->B, 0, as_stream(stream));
     return rc == DPILQR_EUNSUPPORTED ? fail(rc, "backward_pass_fused: no instantiation for n_x=%d", desc->k * desc->n_s) : rc;
@@ -707,6 +725,7 @@ int32_t dpilqr_backward_pass_fused(const dpilqr_batch_desc* desc, const double* 
 int32_t dpilqr_backward_pass_f32(const dpilqr_batch_desc* desc, const float* X, const float* U, const double* mu, float* K,
                                  float* d, void* workspace, void* stream) {
     int32_t rc = check_desc(desc);
+    if (!rc) rc = check_family5(desc, true);
     if (rc) return rc;
     if (desc->B == 0) return DPILQR_OK;
     if (!X || !U || !mu || !K || !d || !workspace) return fail(DPILQR_EINVAL, "backward_pass_f32: NULL pointer");
@@ -717,6 +736,7 @@ int32_t dpilqr_backward_pass_f32(const dpilqr_batch_desc* desc, const float* X, 
 
 int32_t dpilqr_rollout_f32(const dpilqr_batch_desc* desc, const float* x0, const float* U, float* X, double* J, void* stream) {
     int32_t rc = check_desc(desc);
+    if (!rc) rc = check_family5(desc, true);
     if (rc) return rc;
     if (desc->B == 0) return DPILQR_OK;
     if (!x0 || !U || !X || !J) return fail(DPILQR_EINVAL, "rollout_f32: NULL pointer");
@@ -728,6 +748,7 @@ int32_t dpilqr_rollout_f32(const dpilqr_batch_desc* desc, const float* x0, const
 int32_t dpilqr_forward_pass_f32(const dpilqr_batch_desc* desc, const float* X, const float* U, const float* K, const float* d,
                                 const double* alphas, int32_t n_alpha, float* Xn, float* Un, double* Jn, void* stream) {
     int32_t rc = check_desc(desc);
+    if (!rc) rc = check_family5(desc, true);
     if (rc) return rc;
     if (desc->B == 0) return DPILQR_OK;
     if (!X || !U || !K || !d || !alphas || !Xn || !Un || !Jn) return fail(DPILQR_EINVAL, "forward_pass_f32: NULL pointer");

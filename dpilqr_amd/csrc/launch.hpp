@@ -5,7 +5,8 @@
 // batched entry points), tu_big.hip (the sweep for n_x > 60 and the fp32 arm), tu_team.hip (the fused
 // wavefront sweeps with a helper wavefront per item) and dpilqr_hip.hip (the C ABI and the
 // solve loop); round 4 added tu_inprod.hip (the wavefront sweeps with in-sweep production) and tu_lsteam.hip (the line search
-// with two wavefronts per item).  No device code crosses a file boundary.
+// with two wavefronts per item), and tu_bike.hip holds the in-sweep production of the five-state family (BikeDynamics5D).
+// No device code crosses a file boundary.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -36,11 +37,22 @@ inline int32_t allow_lds(Kern kern, size_t bytes) {
     return DPILQR_OK;
 }
 
-// run `body` with the (NS,NC) family as compile-time constants
+// run `body` with the (NS,NC) family as compile-time constants.  DISPATCH_FAMILY: the families of the large-cluster path
+// (tu_big.hip, tu_bigfwd.hip); DISPATCH_FAMILY_ALL adds the five-state family (BikeDynamics5D), which that path does not serve
+// (dpilqr_hip.hip rejects bike clusters with n_x > 60 and the fp32 arm for them before any launcher is reached).
 #define DISPATCH_FAMILY(ns, BODY)                                                         \
     switch (ns) {                                                                         \
     case 3:  { constexpr int NS = 3,  NC = 2; BODY } break;                               \
     case 4:  { constexpr int NS = 4,  NC = 2; BODY } break;                               \
+    case 6:  { constexpr int NS = 6,  NC = 3; BODY } break;                               \
+    case 12: { constexpr int NS = 12, NC = 4; BODY } break;                               \
+    default: return ::dpilqr::fail(DPILQR_EINVAL, "unsupported per-agent state dim %d", (int)(ns)); \
+    }
+#define DISPATCH_FAMILY_ALL(ns, BODY)                                                     \
+    switch (ns) {                                                                         \
+    case 3:  { constexpr int NS = 3,  NC = 2; BODY } break;                               \
+    case 4:  { constexpr int NS = 4,  NC = 2; BODY } break;                               \
+    case 5:  { constexpr int NS = 5,  NC = 2; BODY } break;                               \
     case 6:  { constexpr int NS = 6,  NC = 3; BODY } break;                               \
     case 12: { constexpr int NS = 12, NC = 4; BODY } break;                               \
     default: return ::dpilqr::fail(DPILQR_EINVAL, "unsupported per-agent state dim %d", (int)(ns)); \
@@ -83,9 +95,9 @@ inline bool fused_workgroup_sweep_applies(const dpilqr_batch_desc& D) {
     static const bool off = route_flag("DPILQR_NO_FUSED") || route_flag("DPILQR_NO_FUSED_WG");
     return !off && ((D.n_s == 4 && D.n_c == 2 && D.k >= 6 && D.k <= 15) || (D.n_s == 6 && D.n_c == 3 && D.k >= 2 && D.k <= 10));
 }
-// Wavefront sweep with in-sweep production (riccati_mfma.hpp, PNS; tu_inprod.hip): at most four agents of the six-state family
-// (n_x <= 24) or at most six CarDynamics3D agents (n_x <= 18) -- any models of the family, any per-agent weights, any n_dims --
-// padded into the next instantiated size.
+// Wavefront sweep with in-sweep production (riccati_mfma.hpp, PNS; tu_inprod.hip, tu_bike.hip): at most four agents of the
+// six-state family (n_x <= 24), at most six CarDynamics3D agents (n_x <= 18) or at most four BikeDynamics5D agents (n_x <= 20)
+// -- any models of the family, any per-agent weights, any n_dims -- padded into the next instantiated size.
 inline bool fused_wavefront_inprod_applies(const dpilqr_batch_desc& D) {
     static const bool off = route_flag("DPILQR_NO_FUSED") || route_flag("DPILQR_NO_INPROD");
     static const bool no4 = route_flag("DPILQR_NO_INPROD4");   // A/B switch: the four-state clusters' previous routes
@@ -97,7 +109,7 @@ inline bool fused_wavefront_inprod_applies(const dpilqr_batch_desc& D) {
     // profiles/r04_inprod_four_state.txt)
     if (D.n_s == 4 && D.n_c == 2 && D.k <= 5 && !no4)
         return !fused_wavefront_sweep_applies(D) && !fused_wavefront_general_applies(D);
-    return (D.n_s == 6 && D.n_c == 3 && D.k <= 4) || (D.n_s == 3 && D.n_c == 2 && D.k <= 6);
+    return (D.n_s == 6 && D.n_c == 3 && D.k <= 4) || (D.n_s == 3 && D.n_c == 2 && D.k <= 6) || (D.n_s == 5 && D.n_c == 2 && D.k <= 4);
 }
 inline bool fused_sweep_applies(const dpilqr_batch_desc& D) {
     return fused_wavefront_sweep_applies(D) || fused_wavefront_general_applies(D) || fused_workgroup_sweep_applies(D) ||
@@ -114,7 +126,12 @@ inline bool solve_prefers_records(const dpilqr_batch_desc& D) {
     // round 4: three six-state agents (n_x = 18: 16 % of cfg4's sub-problems) through the (20, 10) wavefront sweep, padded
     // while loading (riccati_mfma.hpp, PAD; DPILQR_RICCATI_NO_PAD switches it off in the launcher)
     // (two .. four six-state agents: records unless the in-sweep producer serves them)
-    if (fused_wavefront_inprod_applies(D)) { static const bool rec = route_flag("DPILQR_INPROD_RECORDS"); return rec; }
+    // (one or two BikeDynamics5D: the producer + the record-fed padded sweep; whole solves of 4096 items 14.6 / 18.8 ms against
+    // 17.5 / 20.8 in-sweep -- four bikes the other way, 42.4 against 33.9; profiles/bike_solves.txt)
+    if (fused_wavefront_inprod_applies(D)) {
+        static const bool rec = route_flag("DPILQR_INPROD_RECORDS");
+        return rec || (!off && D.n_s == 5 && D.k <= 2);
+    }
     return !off && ((D.n_s == 6 && D.n_c == 3 && (D.k == 2 || D.k == 3 || D.k == 4)) || (D.n_s == 4 && D.n_c == 2 && D.k == 6));
 }
 
@@ -142,6 +159,12 @@ int32_t launch_riccati_team(const dpilqr_batch_desc& D, const double* X, const d
 int32_t launch_riccati_inprod(const dpilqr_batch_desc& D, const double* X, const double* U, const double* mu, double* K, double* d,
                               int32_t* singular, const int32_t* items, const int32_t* n_items, int grid_items, int gains_by_item,
                               hipStream_t st);
+
+// ---- tu_bike.hip: the wavefront sweep with in-sweep production for at most four BikeDynamics5D agents (tu_inprod.hip delegates
+// n_s = 5 to it); DPILQR_EUNSUPPORTED, without an error text, for any other batch
+int32_t launch_riccati_bike(const dpilqr_batch_desc& D, const double* X, const double* U, const double* mu, double* K, double* d,
+                            int32_t* singular, const int32_t* items, const int32_t* n_items, int grid_items, int gains_by_item,
+                            hipStream_t st);
 
 // ---- tu_lsteam.hip: the line search with two wavefronts per item (rollout / costs), for launches of at most 1024 items
 int32_t launch_linesearch_team(const dpilqr_batch_desc& D, double* X, double* U, const double* K, const double* d,

@@ -1,4 +1,4 @@
-// models.hpp -- device-side dynamics for the eight reference models.
+// models.hpp -- device-side dynamics for the nine reference models.
 //
 // Replaces the reference's C++/Cython path: bbdynamics.cpp (f_*, linearize_*, rk4,
 // euler_method_discretization) reached through bbdynamicswrap.pyx:61-164.  Written from the
@@ -9,7 +9,8 @@
 // The discretisation the solver uses is applied by the callers:
 //   rollouts : classical RK4, 5 fixed sub-steps (cpp:39-93)            -> integrate<M>()
 //   gains    : forward Euler  A = I + dt*A_c, B = dt*B_c (cpp:95-106)  -> linearize<M>()
-// (the two deliberately differ: reference quirk Q4).
+// (the two deliberately differ: reference quirk Q4).  BikeDynamics5D, a SymbolicModel in the reference, rolls out with ONE
+// RK4 step of dt instead (DynamicalModel.__call__): its ModelDef supplies an integrate of its own.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,15 +29,17 @@ enum Model : int {
     kDoubleInt4D = 0, kDoubleInt6D = 1, kCar3D = 2, kUnicycle4D = 3,
     kQuadcopter6D = 4, kHuman6D = 5, kHumanLin6D = 6, kQuadcopter12D = 7,
     kHumanPad12D = 8,   // this library's own: HumanDynamics6D zero-padded to 12 states / 4 controls (dpilqr_hip.h)
-    kNumModels = 9
+    // 9 is not assigned (model_ns / model_nc answer -1 for it)
+    kBike5D = 10,       // dynamics.py:253-278
+    kNumModels = 11
 };
 
 __host__ __device__ inline int model_ns(int m) {
-    constexpr int t[kNumModels] = {4, 6, 3, 4, 6, 6, 6, 12, 12};
+    constexpr int t[kNumModels] = {4, 6, 3, 4, 6, 6, 6, 12, 12, -1, 5};
     return (m >= 0 && m < kNumModels) ? t[m] : -1;
 }
 __host__ __device__ inline int model_nc(int m) {
-    constexpr int t[kNumModels] = {2, 3, 2, 2, 3, 3, 3, 4, 4};
+    constexpr int t[kNumModels] = {2, 3, 2, 2, 3, 3, 3, 4, 4, -1, 2};
     return (m >= 0 && m < kNumModels) ? t[m] : -1;
 }
 
@@ -390,6 +393,47 @@ __device__ __forceinline__ void rk4_one_guard(F&& run) {
     }
 }
 
+template <> struct ModelDef<kBike5D> {  // x=[px,py,v,theta,phi] u=[a,rho]
+    static constexpr int NS = 5, NC = 2;
+    template <typename R> __device__ static void f(const R* x, const R* u, R* o) {
+        R sn, cs;
+        sincos_r(x[3], &sn, &cs);   // one argument reduction for both (the values of sin(), cos())
+        o[0] = x[2] * cs; o[1] = x[2] * sn; o[2] = u[0]; o[3] = x[2] * tan(x[4]); o[4] = u[1];
+    }
+    // A_c[3][4] = v (tan^2 phi + 1): the form sympy's jacobian gives (SymbolicModel.linearize)
+    template <typename R> __device__ static void jac(const R* x, const R*, R* A, R* B) {
+        const R s = sin(x[3]), c = cos(x[3]), tp = tan(x[4]);
+        A[0 * 5 + 2] = c; A[0 * 5 + 3] = -x[2] * s;
+        A[1 * 5 + 2] = s; A[1 * 5 + 3] = x[2] * c;
+        A[3 * 5 + 2] = tp; A[3 * 5 + 4] = x[2] * (tp * tp + R(1.0));
+        B[2 * 2 + 0] = 1.0; B[4 * 2 + 1] = 1.0;
+    }
+    // rk4_integration(f, x, u, dt, dt) (dynamics.py:18-38, DynamicalModel.__call__): ONE classical step of dt, in the
+    // reference's expression order -- x + 0.5 k dt, x + k2 dt, x + dt (k0 + 2 k1 + 2 k2 + k3) / 6
+    template <typename R> __device__ static void integrate(const R* x, const R* u, R dt, R* xn) {
+        R k0[NS], k1[NS], k2[NS], k3[NS], xb[NS];
+        f(x, u, k0);
+#pragma unroll
+        for (int i = 0; i < NS; ++i) xb[i] = x[i] + (R(0.5) * k0[i]) * dt;
+        f(xb, u, k1);
+#pragma unroll
+        for (int i = 0; i < NS; ++i) xb[i] = x[i] + (R(0.5) * k1[i]) * dt;
+        f(xb, u, k2);
+#pragma unroll
+        for (int i = 0; i < NS; ++i) xb[i] = x[i] + k2[i] * dt;
+        f(xb, u, k3);
+#pragma unroll
+        for (int i = 0; i < NS; ++i) xb[i] = dt * (k0[i] + R(2.0) * k1[i] + R(2.0) * k2[i] + k3[i]);
+        div6_vec<NS>(xb);
+#pragma unroll
+        for (int i = 0; i < NS; ++i) xn[i] = x[i] + xb[i];
+    }
+};
+
+// Models that integrate with a scheme of their own (ModelDef<M>::integrate) rather than the five RK4 sub-steps below
+template <int M> struct HasOwnIntegrate { static constexpr bool value = false; };
+template <> struct HasOwnIntegrate<kBike5D> { static constexpr bool value = true; };
+
 // Models whose only transcendental argument is a heading angle with a CONTROL as its rate (Unicycle4D, Car3D: theta' = u[1],
 // held over the step): ModelDef<M>::kHeading / f_sc.
 template <int M> struct HasHeading { static constexpr bool value = false; };
@@ -407,6 +451,10 @@ template <int M, typename R>
 __device__ inline void integrate(const R* x, const R* u, R dt, R* xn) {
     using D = ModelDef<M>;
     constexpr int NS = D::NS;
+    if constexpr (HasOwnIntegrate<M>::value) {
+        D::integrate(x, u, dt, xn);
+        return;
+    }
     const R dh = dt / 5;
     if constexpr (HasHeading<M>::value) {
         // The heading's slope is the same control in every stage (k0 = k1 = k2 = k3 = u[1] in that component): the heading is
@@ -625,8 +673,10 @@ template <int NS> struct Family;
 #define DPILQR_FAM4(X) X(kDoubleInt4D) X(kUnicycle4D)
 #define DPILQR_FAM6(X) X(kDoubleInt6D) X(kQuadcopter6D) X(kHuman6D) X(kHumanLin6D)
 #define DPILQR_FAM12(X) X(kQuadcopter12D) X(kHumanPad12D)
+#define DPILQR_FAM5(X) X(kBike5D)
 DPILQR_FAMILY(3, DPILQR_FAM3)
 DPILQR_FAMILY(4, DPILQR_FAM4)
+DPILQR_FAMILY(5, DPILQR_FAM5)
 DPILQR_FAMILY(6, DPILQR_FAM6)
 DPILQR_FAMILY(12, DPILQR_FAM12)
 

@@ -178,7 +178,7 @@
                     switch (inp_model) {
                         DPILQR_INP_CASE(kDoubleInt4D) DPILQR_INP_CASE(kDoubleInt6D) DPILQR_INP_CASE(kCar3D) DPILQR_INP_CASE(kUnicycle4D)
                         DPILQR_INP_CASE(kQuadcopter6D) DPILQR_INP_CASE(kHuman6D) DPILQR_INP_CASE(kHumanLin6D)
-                        DPILQR_INP_CASE(kQuadcopter12D) DPILQR_INP_CASE(kHumanPad12D)
+                        DPILQR_INP_CASE(kQuadcopter12D) DPILQR_INP_CASE(kHumanPad12D) DPILQR_INP_CASE(kBike5D)
                         default: break;
                     }
 #undef DPILQR_INP_CASE

@@ -52,6 +52,7 @@ int32_t launch_forward(const dpilqr_batch_desc& D, int mode, const double* x0, d
         DPILQR_TRY_RO(MODEL, 4) DPILQR_TRY_RO(MODEL, 5) DPILQR_TRY_RO(MODEL, 6)
         DPILQR_RO_6(kDoubleInt6D)
         DPILQR_RO_6(kCar3D)
+        DPILQR_RO_6(kBike5D)
         DPILQR_RO_6(kHuman6D)
         DPILQR_RO_6(kHumanLin6D)
         DPILQR_TRY_RO(kQuadcopter12D, 1) DPILQR_TRY_RO(kQuadcopter12D, 2) DPILQR_TRY_RO(kQuadcopter12D, 3)
@@ -94,6 +95,7 @@ int32_t launch_forward(const dpilqr_batch_desc& D, int mode, const double* x0, d
         DPILQR_TRY_WAVE(MODEL, 4) DPILQR_TRY_WAVE(MODEL, 5) DPILQR_TRY_WAVE(MODEL, 6)
         DPILQR_WAVE_6(kDoubleInt6D)
         DPILQR_WAVE_6(kCar3D)
+        DPILQR_WAVE_6(kBike5D)
         DPILQR_WAVE_6(kHuman6D)
         DPILQR_WAVE_6(kHumanLin6D)
         DPILQR_TRY_WAVE(kQuadcopter12D, 1) DPILQR_TRY_WAVE(kQuadcopter12D, 2) DPILQR_TRY_WAVE(kQuadcopter12D, 3)
@@ -108,7 +110,7 @@ int32_t launch_forward(const dpilqr_batch_desc& D, int mode, const double* x0, d
     const int ipb = (!no_pack && threads == 64 && 4 * lds_item <= (size_t)kMaxLds) ? 4 : 1;
     const size_t lds = lds_item * ipb;
     threads *= ipb;
-    DISPATCH_FAMILY(D.n_s, {
+    DISPATCH_FAMILY_ALL(D.n_s, {
         int32_t rc = allow_lds(k_forward<double, NS, NC, false>, lds);
         if (rc) return rc;
         hipLaunchKernelGGL((k_forward<double, NS, NC, false>), dim3((grid_items + ipb - 1) / ipb), dim3(threads), lds, st, D, mode,
@@ -127,7 +129,7 @@ int32_t set_stamp_buffer_forward(void* buf) {
 int32_t launch_model_op(int op, int32_t n, int32_t ns, const int32_t* model, const double* x, const double* u, double dt,
                         double* o1, double* o2, hipStream_t st) {
     const dim3 grid((n + 63) / 64), block(64);
-    DISPATCH_FAMILY(ns, {
+    DISPATCH_FAMILY_ALL(ns, {
         if (op == 0) hipLaunchKernelGGL((k_model_op<NS, NC, 0>), grid, block, 0, st, n, model, x, u, dt, o1, o2);
         else if (op == 1) hipLaunchKernelGGL((k_model_op<NS, NC, 1>), grid, block, 0, st, n, model, x, u, dt, o1, o2);
         else hipLaunchKernelGGL((k_model_op<NS, NC, 2>), grid, block, 0, st, n, model, x, u, dt, o1, o2);
@@ -140,7 +142,7 @@ int32_t launch_cost_eval(const dpilqr_batch_desc& D, int32_t n_pts, const double
                          double* cost, hipStream_t st) {
     const int64_t total = (int64_t)D.B * n_pts;
     const dim3 grid((unsigned)((total + 63) / 64)), block(64);
-    DISPATCH_FAMILY(D.n_s, {
+    DISPATCH_FAMILY_ALL(D.n_s, {
         hipLaunchKernelGGL((k_cost_eval<NS, NC>), grid, block, 0, st, D, n_pts, x, u, terminal, cost);
     })
     HIP_TRY(hipGetLastError());

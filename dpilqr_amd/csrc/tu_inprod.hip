@@ -15,6 +15,8 @@ int32_t launch_riccati_inprod(const dpilqr_batch_desc& D, const double* X, const
                               int32_t* singular, const int32_t* items, const int32_t* n_items, int grid_items, int gains_by_item,
                               hipStream_t st) {
     if (grid_items <= 0 || !fused_wavefront_inprod_applies(D)) return DPILQR_EUNSUPPORTED;
+    // the five-state family (BikeDynamics5D) has a translation unit of its own
+    if (D.n_s == 5) return launch_riccati_bike(D, X, U, mu, K, d, singular, items, n_items, grid_items, gains_by_item, st);
     const int n = D.k * D.n_s, m = D.k * D.n_c;
     static const int max_wv = route_int("DPILQR_MFMA_WAVES", 8);
     const int cus = device_cus();

@@ -48,7 +48,7 @@ int32_t launch_make_tiles(const dpilqr_batch_desc& D, const double* X, const dou
     const int ts = make_tiles_steps(D.k, D.n_s, D.n_c);
     const size_t lds = make_tiles_lds_bytes(D.k, D.n_s, D.n_c, ts);
     dim3 grid((D.T + 1 + ts - 1) / ts, grid_items);
-    DISPATCH_FAMILY(D.n_s, {
+    DISPATCH_FAMILY_ALL(D.n_s, {
         int32_t rc = allow_lds(k_make_tiles<NS, NC, false>, lds);
         if (rc) return rc;
         if (sparse) {

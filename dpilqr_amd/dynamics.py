@@ -1,9 +1,9 @@
 """Dynamics plugins: same class names, constructors and methods as the reference's dpilqr/dynamics.py
-(DynamicalModel :54-92, CppModel :117-130, MultiDynamicalModel :133-202, the eight models :205-250).
+(DynamicalModel :54-92, SymbolicModel :95-114, CppModel :117-130, MultiDynamicalModel :133-202, the nine models :205-278).
 
-The recognised models carry only their `Model` tag; every evaluation happens on the GPU.  A user may
-still subclass DynamicalModel with host code (the reference's BikeDynamics5D is such a plugin): the
-solver then calls that code itself and feeds the GPU sweep with the tiles it returns.
+The recognised models carry only their `Model` tag; every evaluation happens on the GPU -- BikeDynamics5D included, which
+the reference evaluates with sympy on the host.  A user may still subclass DynamicalModel (or SymbolicModel) with host code:
+the solver then calls that code itself and feeds the GPU sweep with the tiles it returns.
 """
 import abc
 
@@ -49,6 +49,30 @@ class DynamicalModel(abc.ABC):
         return f"{type(self).__name__}(n_x: {self.n_x}, n_u: {self.n_u}, id: {self.id})"
 
 
+class SymbolicModel(DynamicalModel):
+    """The reference's mix-in for analytical linearisation (dynamics.py:95-114): a subclass sets self._f, self.A_num and
+    self.B_num (sympy.lambdify of x_dot and its Jacobians, say) in its __init__(dt).  Host code: such a plugin takes the
+    host-plugin path of ilqrSolver.  This package does not import sympy; subclasses do."""
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        del state["A_num"]
+        del state["B_num"]
+        del state["_f"]
+        return state
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        self.__init__(self.dt)
+
+    def f(self, x, u):
+        return self._f(x, u)
+
+    def linearize(self, x, u):
+        """Forward Euler of the continuous Jacobians A_num, B_num."""
+        return np.eye(x.size) + self.dt * self.A_num(x, u), self.dt * self.B_num(x, u)
+
+
 class CppModel(DynamicalModel):
     """A model the HIP library implements (the reference's C++-backed models); `self.model` is its tag."""
 
@@ -85,10 +109,13 @@ HumanDynamicsLin6D = _device_model("HumanDynamicsLin6D", Model.HumanLin6D)
 # QuadcopterDynamics12D (a MultiDynamicalModel needs uniform dims, dynamics.py:165-170).  First 6 states / 3 controls:
 # HumanDynamics6D; the other 6 states never move, the fourth control does nothing.
 HumanDynamics6DPadded12 = _device_model("HumanDynamics6DPadded12", Model.HumanPad12D)
+# The reference's BikeDynamics5D (a SymbolicModel there): x = [p_x, p_y, v, theta, phi], u = [a, rho].  Its rollouts take
+# ONE RK4 step of dt (the reference's DynamicalModel.__call__), its Jacobians forward Euler, like the other models'.
+BikeDynamics5D = _device_model("BikeDynamics5D", Model.Bike5D)
 
 DEVICE_MODEL_CLASSES = (DoubleIntDynamics4D, DoubleIntDynamics6D, CarDynamics3D, UnicycleDynamics4D,
                         QuadcopterDynamics6D, QuadcopterDynamics12D, HumanDynamics6D, HumanDynamicsLin6D,
-                        HumanDynamics6DPadded12)
+                        HumanDynamics6DPadded12, BikeDynamics5D)
 
 
 def is_device_model(m):

@@ -1,6 +1,6 @@
 """Recognise the reference's plugin objects and lower them to device descriptors.
 
-An ilqrProblem whose dynamics are the eight known models (alone or stacked in a MultiDynamicalModel) and
+An ilqrProblem whose dynamics are the known device models (alone or stacked in a MultiDynamicalModel) and
 whose cost is ReferenceCost / GameCost(ReferenceCost..., ProximityCost) is described completely by a few
 small arrays; `lower_problems` turns any number of such problems of ONE shape into a ProblemBatch.
 Anything else (user subclasses with host code) is not lowerable and takes the host-plugin path of

@@ -63,6 +63,11 @@ extern "C" {
  * controls, six padded states that never move (A = 1 on their diagonal, B = 0) and a fourth control that does nothing
  * (give it a small positive R entry, as scripts/examples.py:93 does for the human's unused third control). */
 #define DPILQR_MODEL_HUMAN_PAD_12D 8
+/* BikeDynamics5D (dynamics.py:253-278, a SymbolicModel in the reference): x = [p_x, p_y, v, theta, phi], u = [a, rho],
+ * f = [v cos theta, v sin theta, a, v tan phi, rho].  Unlike the C++ models it integrates with ONE classical RK4 step of dt
+ * (DynamicalModel.__call__); its Jacobians are discretised by forward Euler like theirs.  The only five-state model: the
+ * (n_s, n_c) = (5, 2) family.  Value 9 is not assigned. */
+#define DPILQR_MODEL_BIKE_5D 10
 
 /* per-item solve status (written by dpilqr_solve_batch) */
 #define DPILQR_STATUS_ACTIVE 0
@@ -90,7 +95,7 @@ extern "C" {
 typedef struct dpilqr_batch_desc {
     int32_t B;   /* sub-problems in the batch                                    */
     int32_t k;   /* agents per sub-problem                                       */
-    int32_t n_s; /* per-agent state dim   (3, 4, 6 or 12)                        */
+    int32_t n_s; /* per-agent state dim   (3, 4, 5, 6 or 12)                     */
     int32_t n_c; /* per-agent control dim (2, 3 or 4)                            */
     int32_t T;   /* horizon N (control.py:56)                                    */
     int32_t uniform_model; /* hints, 0 = unknown / mixed (always valid).  Bits 0..7: 1 + Model enum when EVERY agent of
@@ -186,8 +191,8 @@ int32_t dpilqr_backward_pass(const dpilqr_batch_desc* desc, const double* X, con
  * per-agent, per-item Q, R, Q_f;
  * (b) 6..15 agents of the four-state family or 5..10 of the six-state family, any
  * models of the family, any weights (cfg3 / cfg4 clusters: 90 doubles instead of a 94 KB record per step at n_x = 60);
- * (c) 1..4 agents of the six-state family or 1..6 CarDynamics3D agents, any models of the family, any weights, any n_dims
- * (the plugins evaluated inside the padded wavefront sweep).
+ * (c) 1..4 agents of the six-state family, 1..6 CarDynamics3D agents or 1..4 BikeDynamics5D agents, any models of the
+ * family, any weights, any n_dims (the plugins evaluated inside the padded wavefront sweep).
  * DPILQR_EUNSUPPORTED for any other batch (twelve-state agents, four-state clusters of at most five agents without
  * the hints).  dpilqr_solve_batch picks it by itself, and its workspace then holds no records. */
 int32_t dpilqr_backward_pass_fused(const dpilqr_batch_desc* desc, const double* X, const double* U, const double* mu, double* K,
