@@ -224,7 +224,7 @@ def test_window_invariance(dp):
     assert (g["X"] == full["X"]).all().item()
 
 
-@pytest.mark.parametrize("model,k", [(0, 5), (0, 1), (3, 3), (3, 6), (0, 6), (4, 2), (4, 5), (1, 3), (2, 4)])
+@pytest.mark.parametrize("model,k", [(m, k) for m in (0, 3, 4, 1, 2) for k in range(1, 7)])      # the 30 instantiations of tu_lsteam.hip
 def test_line_search_team_equals_the_one_wavefront_line_search(dp, model, k):
     """Launches of at most 1024 items run the line search with a TEAM of two wavefronts per item -- one rolls the candidates out,
     the other evaluates their costs a step behind (forward_team.hpp) -- larger launches one wavefront per item.  Pure scheduling:
@@ -233,6 +233,11 @@ def test_line_search_team_equals_the_one_wavefront_line_search(dp, model, k):
     included."""
     from dpilqr_amd.util import random_setup
     B, Bbig, T = 700, 2600, 40
+    # two pairs whose scenarios would miss the mix the last line asks for (the CPU oracle on the same 700 scenarios: two
+    # DoubleIntDynamics6D agents never reject a first candidate at radius 0.5 -- 36 do at 5.0; six cars accept the first
+    # candidate in 18 % of their iterations at T = 40 -- 50 % at T = 10)
+    radius = 5.0 if (model, k) == (1, 2) else 0.5
+    if (model, k) == (2, 6): T = 10
     ns, nc, nd = {4: (6, 3, 3), 1: (6, 3, 3), 2: (3, 2, 2)}.get(model, (4, 2, 2))
     x0 = np.zeros((Bbig, ns * k)); xf = np.zeros((Bbig, ns * k))
     if k == 1:      # (random_setup normalises by the agents' mutual distances: undefined for one agent)
@@ -245,8 +250,8 @@ def test_line_search_team_equals_the_one_wavefront_line_search(dp, model, k):
     Q = (50.0 * np.eye(6)) if ns == 6 else (np.diag([1.0, 1, 0, 0]) if ns == 4 else np.diag([1.0, 1, 0])); R = np.eye(nc); Qf = 1000.0 * np.eye(ns)
     U0 = np.zeros((Bbig, T, nc * k))
     if model == 4: U0[:, :, 0::3] = 9.80665
-    small = dp.ProblemBatch([model] * k, [nd] * k, xf[:B], Q, R, Qf, 0.5, 0.1, T).solve(x0[:B], U0[:B], trace=True, window=B)
-    big = dp.ProblemBatch([model] * k, [nd] * k, xf, Q, R, Qf, 0.5, 0.1, T).solve(x0, U0, trace=True, window=Bbig)
+    small = dp.ProblemBatch([model] * k, [nd] * k, xf[:B], Q, R, Qf, radius, 0.1, T).solve(x0[:B], U0[:B], trace=True, window=B)
+    big = dp.ProblemBatch([model] * k, [nd] * k, xf, Q, R, Qf, radius, 0.1, T).solve(x0, U0, trace=True, window=Bbig)
     for key in ("X", "U", "J", "status", "n_bwd", "n_fwd"):
         assert (small[key] == big[key][:B]).all().item(), key
     ts, tb = small["trace"].cpu().numpy(), big["trace"].cpu().numpy()
