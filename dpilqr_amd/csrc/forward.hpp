@@ -556,7 +556,7 @@ __device__ R horizon_pass(const dpilqr_batch_desc& D, const ItemParams& P, bool 
 //                   (control.py:179-211) and the copy of the accepted candidate into X, U.
 // Workgroup layout: `ipb` sub-problems per workgroup.  When a sub-problem's threads fit one wavefront
 // (n_alpha * k <= 64, e.g. cfg2's 50) four of them share a 256-thread workgroup, one wave each with its own
-// LDS slice and no workgroup barrier -- the same SIMD-placement argument as for the sweep (riccati_tiled.hpp).
+// LDS slice and no workgroup barrier -- the same SIMD-placement argument as for the sweep (riccati_mfma.hpp).
 // R: arithmetic type; KDIRECT: K[t] is not staged in LDS (large clusters); lds_per_item in elements of R.
 // the launcher's test for the matrix-pipe form of K[t] dx (KDIRECT, candidates / line-search mode): row tiles of 16 controls, at most
 // two per wavefront; the candidates are a tile's columns

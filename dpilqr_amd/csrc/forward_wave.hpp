@@ -18,7 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "forward.hpp"
-#include "riccati_tiled.hpp"   // v2d, store_v2d_nt
+#include "wave_util.hpp"   // v2d, store_v2d_nt
 
 namespace dpilqr {
 

@@ -2,10 +2,11 @@
 //
 // The library is built from several .hip files so that they compile in parallel (one file with every kernel
 // instantiation took over two minutes): tu_tiles.hip (K1), tu_riccati.hip (K2), tu_forward.hip (K3, rollouts, the small
-// batched entry points), tu_big.hip (the sweep for n_x > 60 and the fp32 arm), tu_team.hip (the fused
-// wavefront sweeps with a helper wavefront per item) and dpilqr_hip.hip (the C ABI and the
-// solve loop); round 4 added tu_inprod.hip (the wavefront sweeps with in-sweep production) and tu_lsteam.hip (the line search
-// with two wavefronts per item), and tu_bike.hip holds the in-sweep production of the five-state family (BikeDynamics5D).
+// batched entry points), tu_big.hip (the sweep for n_x > 60 and the fp32 arm), tu_bigfwd.hip (their forward passes),
+// tu_team.hip (the fused wavefront sweeps with a helper wavefront per item), tu_inprod.hip (the wavefront sweeps with in-sweep
+// production), tu_bike.hip (the same for the five-state family, BikeDynamics5D), tu_lsteam.hip (the line search with two
+// wavefronts per item), tu_frontend.hip (the device-side dispatch front / back end) and dpilqr_hip.hip (the C ABI and the
+// solve loop).
 // No device code crosses a file boundary.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -40,23 +41,15 @@ inline int32_t allow_lds(Kern kern, size_t bytes) {
 // run `body` with the (NS,NC) family as compile-time constants.  DISPATCH_FAMILY: the families of the large-cluster path
 // (tu_big.hip, tu_bigfwd.hip); DISPATCH_FAMILY_ALL adds the five-state family (BikeDynamics5D), which that path does not serve
 // (dpilqr_hip.hip rejects bike clusters with n_x > 60 and the fp32 arm for them before any launcher is reached).
-#define DISPATCH_FAMILY(ns, BODY)                                                         \
-    switch (ns) {                                                                         \
-    case 3:  { constexpr int NS = 3,  NC = 2; BODY } break;                               \
-    case 4:  { constexpr int NS = 4,  NC = 2; BODY } break;                               \
-    case 6:  { constexpr int NS = 6,  NC = 3; BODY } break;                               \
-    case 12: { constexpr int NS = 12, NC = 4; BODY } break;                               \
-    default: return ::dpilqr::fail(DPILQR_EINVAL, "unsupported per-agent state dim %d", (int)(ns)); \
-    }
-#define DISPATCH_FAMILY_ALL(ns, BODY)                                                     \
-    switch (ns) {                                                                         \
-    case 3:  { constexpr int NS = 3,  NC = 2; BODY } break;                               \
-    case 4:  { constexpr int NS = 4,  NC = 2; BODY } break;                               \
-    case 5:  { constexpr int NS = 5,  NC = 2; BODY } break;                               \
-    case 6:  { constexpr int NS = 6,  NC = 3; BODY } break;                               \
-    case 12: { constexpr int NS = 12, NC = 4; BODY } break;                               \
-    default: return ::dpilqr::fail(DPILQR_EINVAL, "unsupported per-agent state dim %d", (int)(ns)); \
-    }
+#define DISPATCH_FAMILY_CASE(NS_, NC_, ...) case NS_: { constexpr int NS = NS_, NC = NC_; __VA_ARGS__ } break;
+#define DISPATCH_FAMILY_CASES(ns, ...)                                                    \
+    DISPATCH_FAMILY_CASE(3, 2, __VA_ARGS__)                                               \
+    DISPATCH_FAMILY_CASE(4, 2, __VA_ARGS__)                                               \
+    DISPATCH_FAMILY_CASE(6, 3, __VA_ARGS__)                                               \
+    DISPATCH_FAMILY_CASE(12, 4, __VA_ARGS__)                                              \
+    default: return ::dpilqr::fail(DPILQR_EINVAL, "unsupported per-agent state dim %d", (int)(ns));
+#define DISPATCH_FAMILY(ns, BODY) switch (ns) { DISPATCH_FAMILY_CASES(ns, BODY) }
+#define DISPATCH_FAMILY_ALL(ns, BODY) switch (ns) { DISPATCH_FAMILY_CASE(5, 2, BODY) DISPATCH_FAMILY_CASES(ns, BODY) }
 
 // compute units of the current device (256 on MI355X): the sweep deals its items over rounds of this many workgroups
 int device_cus();
@@ -150,6 +143,38 @@ int32_t launch_riccati_fused(const dpilqr_batch_desc& D, const double* X, const 
                              double* d, int32_t* singular, const int32_t* items, const int32_t* n_items, int grid_items,
                              int gains_by_item, hipStream_t st);
 int32_t set_stamp_buffer_riccati(void* device_buffer);
+
+// ---- the launch of a wavefront sweep (riccati_mfma.hpp), for tu_riccati.hip, tu_inprod.hip, tu_bike.hip and tu_team.hip.
+// Wavefronts per workgroup = per CU: 4 (one per SIMD), or 8 / 12 (two / three per SIMD) when the launch has the items for them,
+// DPILQR_MFMA_WAVES (max_wv) allows them and they fit the CU's LDS.  tier12: the kernel family has a 12-wavefront
+// instantiation for this launch (the record-fed sweep: for block-diagonal tiles only).
+constexpr int sweep_waves(int grid_items, int max_wv, size_t lds_per_wave, bool tier12) {
+    return (tier12 && grid_items > 2048 && max_wv >= 12 && lds_per_wave * 12 <= (size_t)kMaxLds) ? 12
+           : (grid_items > 1024 && max_wv >= 8 && lds_per_wave * 8 <= (size_t)kMaxLds) ? 8 : 4;
+}
+// whole rounds of one workgroup per CU; the kernel deals the live items over them (riccati_mfma.hpp)
+constexpr int sweep_grid(int grid_items, int cus, int wv) {
+    return grid_items <= cus ? grid_items : (grid_items + cus * wv - 1) / (cus * wv) * cus;
+}
+inline int sweep_max_waves() { static const int v = route_int("DPILQR_MFMA_WAVES", 12); return v; }
+// one instantiation, `wv` sweeping wavefronts per workgroup of `threads`; `args` are the kernel's, `cus` among them
+template <typename Kern, typename... Args>
+int32_t launch_sweep_kernel(Kern kern, int wv, int threads, size_t lds, int grid_items, int cus, hipStream_t st, const Args&... args) {
+    const int32_t rc = allow_lds(kern, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(kern, dim3(sweep_grid(grid_items, cus, wv)), dim3(threads), lds, st, args...);
+    HIP_TRY(hipGetLastError());
+    g_sweep_waves = wv;
+    return DPILQR_OK;
+}
+// a kernel family's instantiations for 4, 8 and 12 wavefronts (k12 = nullptr: none); lds_per_wave in bytes
+template <typename T> struct same_type { using type = T; };
+template <typename Kern, typename... Args>
+int32_t launch_wave_sweep(Kern k4, typename same_type<Kern>::type k8, typename same_type<Kern>::type k12, size_t lds_per_wave,
+                          int grid_items, int cus, hipStream_t st, const Args&... args) {
+    const int wv = sweep_waves(grid_items, sweep_max_waves(), lds_per_wave, k12 != nullptr);
+    return launch_sweep_kernel(wv == 12 ? k12 : (wv == 8 ? k8 : k4), wv, 64 * wv, lds_per_wave * wv, grid_items, cus, st, args...);
+}
 // ---- tu_team.hip: the fused wavefront sweeps with a helper wavefront per item, for launches of at most 1024 items
 int32_t launch_riccati_team(const dpilqr_batch_desc& D, const double* X, const double* U, const double* mu, double* K, double* d,
                             int32_t* singular, const int32_t* items, const int32_t* n_items, int grid_items, int gains_by_item,

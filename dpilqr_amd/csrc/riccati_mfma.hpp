@@ -1,9 +1,20 @@
 // riccati_mfma.hpp -- K2 for n_x <= 20: the Riccati backward sweep with one wavefront per sub-problem, up to three
 // per SIMD (ilqrSolver._backward_pass, control.py:116-148).  The dominant kernel of the cfg2 benchmark.
 //
-// Data flow, LDS residency and record prefetching are those of riccati_tiled.hpp (the previous, all-vector-pipe
-// version, kept as a fallback).  What differs:
+// Same recursion as riccati.hpp (see the equations there); this kernel is the fast path for the sizes it is instantiated
+// for.  Design, for n = n_x, m = n_u known at compile time:
 //
+//  * the value function [P | p] stays in LDS for the whole horizon; nothing but the tile records is read from HBM and
+//    nothing but K[t], d[t] is written.
+//  * each step's record is fetched ONE STEP AHEAD straight into registers (16-byte loads issued at the top of step t for
+//    record t-1, consumed at the top of step t-1), so the HBM latency hides under the arithmetic of a whole step; only
+//    [A|B] (used by two products) is then parked in LDS.
+//  * no workgroup barriers: a workgroup is WAVES independent wavefronts, each sweeping its own sub-problem out of its own
+//    LDS slice, and a single wavefront executes its LDS operations in order.  Packing at least four of them into one
+//    workgroup is placement control, not cooperation: a workgroup's wavefronts are dealt one per SIMD, whereas 1024
+//    single-wavefront workgroups were observed (in-kernel HW_ID stamps) to land two-on-a-SIMD on ~17 % of the CUs whenever
+//    the preceding kernel had left the dispatcher's SIMD rotation in an odd state -- and the sweep is issue-bound, so two
+//    wavefronts on one SIMD run at half speed and the launch takes 1.4x as long.
 //  * the dense products are v_mfma_f64_16x16x4_f64 tiles.  Measured on MI355X (scripts/ubench/mfma_f64.hip): the
 //    fp64 MFMA delivers the SAME peak FMA rate as the vector ALU (64 cycles per instruction per SIMD = 16 FMA/clk)
 //    and shares that pipe, so it buys issue slots and operand reads (one MFMA replaces 16 vector FMAs and their LDS
@@ -34,7 +45,8 @@
 
 #include <type_traits>
 
-#include "riccati_tiled.hpp"
+#include "tiles.hpp"
+#include "wave_util.hpp"
 
 namespace dpilqr {
 
@@ -615,7 +627,10 @@ __device__ __forceinline__ void riccati_mfma_sweep(
         prefetch_l(T - 1);
     }
     }
-    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): see riccati_tiled.hpp
+    // Drain the prologue's loads here, once.  Otherwise the loop header merges "prologue order" (which the scheduler is free
+    // to permute) with the loop's own issue order, and the only wait that is safe for both is vmcnt(0) on every iteration;
+    // with nothing pending on entry the in-loop waits stay counted.
+    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0), expcnt/lgkmcnt untouched
     }
 
 #ifdef DPILQR_PHASE_STAMPS

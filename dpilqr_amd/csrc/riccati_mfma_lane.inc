@@ -44,7 +44,7 @@
     const int gLxx = L.oLxx + g * N + c16;           // + 16 jt + (row const) * N
     const int gUG = L.oLuu + g * L.ldUG;             // + colG[jt] + (row const) * ldUG
     const int gLxu = L.oLx + g;                      // [l_x ; l_u][i']
-    // [A|B] prefetch -> LDS, S3 epilogue patterns (as in riccati_tiled.hpp)
+    // [A|B] prefetch -> LDS (16-byte pairs, round-robin over the wavefront; surplus lanes store to sTrash), S3 epilogue patterns
     double* sTrash = lds + C::oEnd;
     double* ab_dst[C::AB_ROUNDS];
     int ab_src[C::AB_ROUNDS];

@@ -13,13 +13,13 @@
 //   * L_xx is written as whole rows in 16-byte pieces (its zeros included): full lines to HBM instead of the generic
 //     kernel's scattered 8-byte entries; L_x, L_u and -- unless DYN_ONLY, see tiles.hpp -- the agents' A, B, L_uu blocks
 //     follow;
-//   * stores are issued behind the compiler's back (riccati_tiled.hpp) so the next group's loads are never made
+//   * stores are issued behind the compiler's back (wave_util.hpp) so the next group's loads are never made
 //     to wait for them by count.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "riccati_tiled.hpp"
 #include "tiles.hpp"
+#include "wave_util.hpp"
 
 namespace dpilqr {
 

@@ -26,24 +26,15 @@ int32_t launch_riccati_bike(const dpilqr_batch_desc& D, const double* X, const d
                             hipStream_t st) {
     if (grid_items <= 0 || D.n_s != 5 || D.n_c != 2 || !fused_wavefront_inprod_applies(D)) return DPILQR_EUNSUPPORTED;
     const int n = D.k * D.n_s, m = D.k * D.n_c;
-    static const int max_wv = route_int("DPILQR_MFMA_WAVES", 8);
     const int cus = device_cus();
 #define DPILQR_TRY_BIKE(NN, MM)                                                                                    \
     if (n <= NN && m <= MM) {                                                                                      \
         static_assert(MfmaCfg<NN, MM>::supported, "MFMA sweep not available for this size");                       \
         static_assert(NN % 5 != 0 || MM * 5 != NN * InprodCfg<NN, MM, 5>::PNC, "every bike cluster is padded");    \
         constexpr size_t per_wave = sizeof(double) * (MfmaCfg<NN, MM>::total + InprodCfg<NN, MM, 5>::total);       \
-        const int wv = (grid_items > 1024 && max_wv >= 8 && per_wave * 8 <= (size_t)kMaxLds) ? 8 : 4;              \
-        const size_t lds_t = per_wave * wv;                                                                        \
-        auto kern = wv == 8 ? k_riccati_bike_inprod<NN, MM, 8> : k_riccati_bike_inprod<NN, MM, 4>;                 \
-        int32_t rc_t = allow_lds(kern, lds_t);                                                                     \
-        if (rc_t) return rc_t;                                                                                     \
-        const int grid = grid_items <= cus ? grid_items : (grid_items + cus * wv - 1) / (cus * wv) * cus;          \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * wv), lds_t, st, D.B, D.T, mu, K, d, singular, items,         \
-                           n_items, gains_by_item, cus, FusedArgs{D, X, U}, n, m);                                 \
-        HIP_TRY(hipGetLastError());                                                                                \
-        g_sweep_waves = wv;                                                                                        \
-        return DPILQR_OK;                                                                                          \
+        return launch_wave_sweep(k_riccati_bike_inprod<NN, MM, 4>, k_riccati_bike_inprod<NN, MM, 8>, nullptr, per_wave, \
+                                 grid_items, cus, st, D.B, D.T, mu, K, d, singular, items, n_items, gains_by_item, cus, \
+                                 FusedArgs{D, X, U}, n, m);                                                        \
     }
     // one bike (5, 2) -> (8, 4); two (10, 4) -> (12, 6); three (15, 6) -> (16, 8); four (20, 8) -> (20, 10)
     DPILQR_TRY_BIKE(8, 4) DPILQR_TRY_BIKE(12, 6) DPILQR_TRY_BIKE(16, 8) DPILQR_TRY_BIKE(20, 10)

@@ -18,25 +18,16 @@ int32_t launch_riccati_inprod(const dpilqr_batch_desc& D, const double* X, const
     // the five-state family (BikeDynamics5D) has a translation unit of its own
     if (D.n_s == 5) return launch_riccati_bike(D, X, U, mu, K, d, singular, items, n_items, grid_items, gains_by_item, st);
     const int n = D.k * D.n_s, m = D.k * D.n_c;
-    static const int max_wv = route_int("DPILQR_MFMA_WAVES", 8);
     const int cus = device_cus();
+    // (the sizes are tried in ascending order: an exact-size instantiation only ever sees clusters of exactly its size)
 #define DPILQR_TRY_INPROD(NN, MM, PNS_)                                                                            \
     if (D.n_s == PNS_ && n <= NN && m <= MM) {                                                                     \
         static_assert(MfmaCfg<NN, MM>::supported, "MFMA sweep not available for this size");                       \
         constexpr size_t per_wave = sizeof(double) * (MfmaCfg<NN, MM>::total + InprodCfg<NN, MM, PNS_>::total);    \
-        const int wv = (grid_items > 1024 && max_wv >= 8 && per_wave * 8 <= (size_t)kMaxLds) ? 8 : 4;              \
-        const size_t lds_t = per_wave * wv;                                                                        \
         constexpr bool PAD_ = (NN % PNS_ != 0) || (MM * PNS_ != NN * InprodCfg<NN, MM, PNS_>::PNC);                \
-        /* (the sizes are tried in ascending order: an exact-size instantiation only ever sees clusters of exactly its size) */ \
-        auto kern = wv == 8 ? k_riccati_mfma_inprod<NN, MM, 8, PNS_, PAD_> : k_riccati_mfma_inprod<NN, MM, 4, PNS_, PAD_>;  \
-        int32_t rc_t = allow_lds(kern, lds_t);                                                                     \
-        if (rc_t) return rc_t;                                                                                     \
-        const int grid = grid_items <= cus ? grid_items : (grid_items + cus * wv - 1) / (cus * wv) * cus;          \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * wv), lds_t, st, D.B, D.T, mu, K, d, singular, items,         \
-                           n_items, gains_by_item, cus, FusedArgs{D, X, U}, n, m);                                 \
-        HIP_TRY(hipGetLastError());                                                                                \
-        g_sweep_waves = wv;                                                                                        \
-        return DPILQR_OK;                                                                                          \
+        return launch_wave_sweep(k_riccati_mfma_inprod<NN, MM, 4, PNS_, PAD_>, k_riccati_mfma_inprod<NN, MM, 8, PNS_, PAD_>, \
+                                 nullptr, per_wave, grid_items, cus, st, D.B, D.T, mu, K, d, singular, items, n_items, \
+                                 gains_by_item, cus, FusedArgs{D, X, U}, n, m);                                    \
     }
     // six-state family: one agent (6, 3) -> (8, 4); two (12, 6); three (18, 9) -> (20, 10); four (24, 12)
     DPILQR_TRY_INPROD(8, 4, 6) DPILQR_TRY_INPROD(12, 6, 6) DPILQR_TRY_INPROD(20, 10, 6) DPILQR_TRY_INPROD(24, 12, 6)

@@ -20,19 +20,12 @@ int32_t launch_riccati_team(const dpilqr_batch_desc& D, const double* X, const d
     if (off || grid_items <= 0) return DPILQR_EUNSUPPORTED;
     const int n = D.k * D.n_s, m = D.k * D.n_c;
     const int cus = device_cus();
-    const int grid = grid_items <= cus ? grid_items : (grid_items + cus * 4 - 1) / (cus * 4) * cus;
+    // four sweeping wavefronts and their four helpers per workgroup
 #define DPILQR_TRY_TEAM(NN, MM, FU)                                                                                \
-    if (n == NN && m == MM) {                                                                                      \
-        using CF = MfmaCfg<NN, MM, FU, true>;                                                                      \
-        const size_t lds_t = sizeof(double) * CF::total * 4;                                                       \
-        auto kern = k_riccati_mfma_team<NN, MM, FU>;                                                               \
-        int32_t rc_t = allow_lds(kern, lds_t);                                                                     \
-        if (rc_t) return rc_t;                                                                                     \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds_t, st, D.B, D.T, mu, K, d, singular, items, n_items,    \
-                           gains_by_item, cus, FusedArgs{D, X, U});                                                \
-        HIP_TRY(hipGetLastError());                                                                                \
-        return DPILQR_OK;                                                                                          \
-    }
+    if (n == NN && m == MM)                                                                                        \
+        return launch_sweep_kernel(k_riccati_mfma_team<NN, MM, FU>, 4, 512, sizeof(double) * MfmaCfg<NN, MM, FU, true>::total * 4, \
+                                   grid_items, cus, st, D.B, D.T, mu, K, d, singular, items, n_items, gains_by_item, cus, \
+                                   FusedArgs{D, X, U});
 #define DPILQR_TRY_TEAM1(NN, MM) DPILQR_TRY_TEAM(NN, MM, 1)
 #define DPILQR_TRY_TEAM2(NN, MM) DPILQR_TRY_TEAM(NN, MM, 2)
     if (fused_wavefront_sweep_applies(D)) {

@@ -8,7 +8,7 @@ from collections import Counter
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
-pat = sys.argv[1] if len(sys.argv) > 1 else "k_riccati_tiledILi20ELi10"
+pat = sys.argv[1] if len(sys.argv) > 1 else "k_riccati_mfmaILi20ELi10"
 out = Path("/tmp/dpilqr.s")
 subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                 f"-I{ROOT/'include'}", f"-I{ROOT/'dpilqr_amd'/'csrc'}", "-S", "--cuda-device-only", "-o", str(out),
