@@ -17,5 +17,5 @@ from .dynamics import (BikeDynamics5D, CarDynamics3D, CppModel, DoubleIntDynamic
                        QuadcopterDynamics6D, QuadcopterDynamics12D, SymbolicModel, UnicycleDynamics4D)
 from .problem import _reset_ids, ilqrProblem, solve_subproblem  # noqa: F401
 from .util import (Point, compute_energy, compute_pairwise_distance, compute_pairwise_distance_nd, distance_to_goal,  # noqa: F401
-                   normalize_energy, perturb_state, pos_mask, random_setup, randomize_locs, split_agents,
+                   normalize_energy, perturb_state, perturbed_starts, pos_mask, random_setup, randomize_locs, split_agents,
                    split_agents_gen, split_graph, uniform_block_diag, π)

@@ -93,6 +93,11 @@ SIGNATURES = {
     "dpilqr_random_setup": (i32, [i32, i64, i32, i32, i32, f64, f64, vp, vp, vp]),
 }
 
+# additive entry points of the extension headers dpilqr_hip.h includes (include/dpilqr_policy.h); bound by load() like the rest
+EXT_SIGNATURES = {
+    "dpilqr_policy_rollout": (i32, [_DP, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+}
+
 MAX_AGENTS = 64
 
 
@@ -112,7 +117,7 @@ def load():
             raise ImportError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                               "(hipcc --offload-arch=gfx950).  dpilqr_amd has no CPU fallback.")
         lib = C.CDLL(str(LIB_PATH))
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES}.items():
             fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -8,6 +8,7 @@ Python objects on the hot path:
     ilqrSolver._backward_pass  control.py:116-148  -> ProblemBatch.make_tiles + backward_pass_tiles
     ilqrSolver._forward_pass   control.py:95-114   -> ProblemBatch.forward_pass
     ilqrSolver.solve           control.py:150-225  -> ProblemBatch.solve
+    (no reference counterpart: the feedback policy closed loop)  -> ProblemBatch.policy_rollout
 """
 import ctypes as C
 import os
@@ -274,6 +275,49 @@ class ProblemBatch:
         fn = self._lib.dpilqr_forward_pass if dtype == torch.float64 else self._lib.dpilqr_forward_pass_f32
         _lib.check(fn(self._d, ptr(X), ptr(U), ptr(K), ptr(d), ptr(al), A, ptr(Xn), ptr(Un), ptr(Jn), stream_handle()))
         return Xn, Un, Jn
+
+    def _policy_shapes(self, X, U, K, x0s, W, u_lim):
+        """Host-side validation of policy_rollout's arguments (no device access): returns the number of samples per item."""
+        B, T, n, m = self.B, self.T, self.n_x, self.n_u
+        if n > 60:
+            raise ValueError(f"policy_rollout serves clusters up to n_x = 60, this batch has n_x = {n}")
+        shape = lambda a: tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)
+        for name, a, want in (("X", X, (B, T + 1, n)), ("U", U, (B, T, m)), ("K", K, (B, T, m, n))):
+            if shape(a) != want:
+                raise ValueError(f"policy_rollout: {name} has shape {shape(a)}, expected {want}")
+        sx = shape(x0s)
+        if len(sx) != 3 or sx[0] != B or sx[2] != n or sx[1] < 1:
+            raise ValueError(f"policy_rollout: x0s has shape {sx}, expected ({B}, n_samples >= 1, {n})")
+        S = int(sx[1])
+        if W is not None and shape(W) != (B, S, T, n):
+            raise ValueError(f"policy_rollout: W has shape {shape(W)}, expected {(B, S, T, n)}")
+        if u_lim is not None:
+            if shape(u_lim) != (2, m):
+                raise ValueError(f"policy_rollout: u_lim has shape {shape(u_lim)}, expected {(2, m)} (lower row, upper row)")
+            lim = u_lim.cpu().numpy() if isinstance(u_lim, torch.Tensor) else np.asarray(u_lim, dtype=np.float64)
+            if not bool((lim[0] <= lim[1]).all()):
+                raise ValueError("policy_rollout: u_lim has a lower limit above its upper limit")
+        return S
+
+    def policy_rollout(self, X, U, K, x0s, W=None, u_lim=None, trajectories=False):
+        """The closed-loop ensemble rollout (dpilqr_policy_rollout): every item's feedback policy u_t = U[t] + K[t] (x_t - X[t])
+        run from S starts at once.  X (B,T+1,n_x), U (B,T,n_u), K (B,T,n_u,n_x): nominal and gains (backward_pass at that
+        nominal); x0s (B,S,n_x); W (B,S,T,n_x) additive disturbance on x_{t+1} or None; u_lim (2,n_u) lower / upper control
+        limits shared by all items or None.  Returns a dict of device tensors: J (B,S), min_sep (B,S), goal_dist (B,S,k) and,
+        with trajectories=True, X (B,S,T+1,n_x), U (B,S,T,n_u)."""
+        S = self._policy_shapes(X, U, K, x0s, W, u_lim)
+        B, T, n, m = self.B, self.T, self.n_x, self.n_u
+        X = self._in(X, (B, T + 1, n)); U = self._in(U, (B, T, m)); K = self._in(K, (B, T, m, n))
+        x0s = self._in(x0s, (B, S, n))
+        W = None if W is None else self._in(W, (B, S, T, n))
+        u_lim = None if u_lim is None else self._in(u_lim, (2, m))
+        out = dict(J=empty((B, S)), min_sep=empty((B, S)), goal_dist=empty((B, S, self.k)))
+        if trajectories:
+            out["X"] = empty((B, S, T + 1, n)); out["U"] = empty((B, S, T, m))
+        _lib.check(self._lib.dpilqr_policy_rollout(self._d, ptr(X), ptr(U), ptr(K), S, ptr(x0s), ptr(W), ptr(u_lim),
+                                                   ptr(out.get("X")), ptr(out.get("U")), ptr(out["J"]), ptr(out["min_sep"]),
+                                                   ptr(out["goal_dist"]), stream_handle()))
+        return out
 
     def cost(self, x, u, terminal=False):
         """GameCost.__call__ at n_pts points per item: x (B,n_pts,n_x), u (B,n_pts,n_u) -> (B,n_pts)."""

@@ -107,6 +107,33 @@ class ilqrSolver:
             K, d = backward_pass_tiles(self._host_tiles(X, U), 1, self.N, self.n_x, self.n_u, self.μ)
         return K[0].cpu().numpy(), d[0].cpu().numpy()
 
+    # ---- the policy, closed loop
+    def closed_loop(self, X, U, x0s, W=None, u_lim=None, mu=0.0, trajectories=False):
+        """Run the feedback policy u_t = U[t] + K[t] (x_t - X[t]) of the trajectory (X, U) from every start in x0s (S, n_x),
+        on the device in one launch (ProblemBatch.policy_rollout): W (S, N, n_x) is an additive disturbance on x_{t+1}, u_lim
+        (2, n_u) lower / upper control limits.  Returns host arrays J (S,), min_sep (S,), goal_dist (S, n_agents) and, with
+        trajectories=True, X (S, N+1, n_x), U (S, N, n_u).
+
+        The gains come from ONE backward pass at the given (X, U) with regularisation mu, so that they belong to that
+        trajectory.  The K_out a solve hands back does not: it is the gain of the solve's LAST backward pass, taken at the
+        iterate BEFORE the last accepted step -- which is why this recomputes instead of reusing it.
+
+        Device problems only: a problem with host plugins (user subclasses of DynamicalModel / Cost) has no device model to
+        step."""
+        if not self.on_device:
+            raise NotImplementedError("closed_loop runs the policy on the device and needs a problem built from the recognised "
+                                      "plugin types: this one contains host plugins, whose dynamics and cost only exist as "
+                                      "Python callables")
+        X = np.asarray(X, dtype=np.float64); U = np.asarray(U, dtype=np.float64)
+        x0s = np.asarray(x0s, dtype=np.float64)
+        if x0s.ndim != 2 or x0s.shape[1] != self.n_x:
+            raise ValueError(f"closed_loop: x0s has shape {x0s.shape}, expected (n_samples, {self.n_x})")
+        pb = self._pb(self.N)
+        K, _ = pb.backward_pass(X[None], U[None], float(mu))
+        r = pb.policy_rollout(X[None], U[None], K, x0s[None], W=None if W is None else np.asarray(W, dtype=np.float64)[None],
+                              u_lim=u_lim, trajectories=trajectories)
+        return {key: v[0].cpu().numpy() for key, v in r.items()}
+
     # ---- the solve
     def solve(self, x0, U=None, n_lqr_iter=50, tol=1e-3, t_kill=None, verbose=True):
         if U is None:

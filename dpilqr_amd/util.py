@@ -172,6 +172,17 @@ def perturb_state(x, x_dims, n_d=2, var=0.5):
     return x
 
 
+def perturbed_starts(x0, x_dims, n_samples, n_d=2, var=0.5, seed=None):
+    """(n_samples, n_x) starts around x0 for a closed-loop ensemble (ilqrSolver.closed_loop, ProblemBatch.policy_rollout): row i
+    is what the i-th call of perturb_state(x0, x_dims, n_d, var) returns after np.random.seed(seed) -- host NumPy, the legacy
+    global stream, so that the ensemble is the one a loop over the reference's perturb_state draws.  seed=None: the stream as
+    it stands."""
+    if seed is not None:
+        np.random.seed(seed)
+    x0 = np.asarray(x0, dtype=np.float64)
+    return np.stack([perturb_state(x0, x_dims, n_d=n_d, var=var).reshape(-1) for _ in range(int(n_samples))])
+
+
 def random_setup_batch(seeds, n_agents, n_states, var, n_d=2, energy=None):
     """(x0, xf) device tensors (S, n_agents * n_states) of the scenarios np.random.seed(s); random_setup(n_agents, n_states,
     is_rotation=False, var=var, n_d=n_d, random=True, energy=energy) for s in range(seeds[0], seeds[0] + S) -- generated on

@@ -202,6 +202,11 @@ int32_t dpilqr_backward_pass_fused(const dpilqr_batch_desc* desc, const double* 
 int32_t dpilqr_forward_pass(const dpilqr_batch_desc* desc, const double* X, const double* U, const double* K,
                             const double* d, const double* alphas, int32_t n_alpha, double* Xn, double* Un,
                             double* Jn, void* stream);
+/* -------------------------------------------------- (4b) the closed-loop ensemble rollout: dpilqr_policy_rollout
+ * An additive entry point (the ABI version stays): declared, with its semantics, in the extension header below, which is part
+ * of this header for every includer.  The identical-ABI CPU twin of the test suite covers the symbols named in this file. */
+#include "dpilqr_policy.h"
+
 /* the float32-rounded line-search table of control.py:162 (host array of DPILQR_N_ALPHA doubles) */
 int32_t dpilqr_alphas(double* alphas_host);
 
