@@ -96,6 +96,8 @@ SIGNATURES = {
 # additive entry points of the extension headers dpilqr_hip.h includes (include/dpilqr_policy.h); bound by load() like the rest
 EXT_SIGNATURES = {
     "dpilqr_policy_rollout": (i32, [_DP, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "dpilqr_policy_rollout_dec": (i32, [_DP, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "dpilqr_dispatch_stitch_policy": (i32, [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 MAX_AGENTS = 64
@@ -105,6 +107,12 @@ class BucketResults(C.Structure):
     """struct dpilqr_bucket_results"""
     _fields_ = [("X", vp * (MAX_AGENTS + 1)), ("U", vp * (MAX_AGENTS + 1)), ("first", i32 * (MAX_AGENTS + 1)),
                 ("count", i32 * (MAX_AGENTS + 1))]
+
+
+class BucketGains(C.Structure):
+    """struct dpilqr_bucket_gains (include/dpilqr_policy.h)"""
+    _fields_ = [("K", vp * (MAX_AGENTS + 1))]
+
 
 _lib = None
 

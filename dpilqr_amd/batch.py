@@ -8,7 +8,7 @@ Python objects on the hot path:
     ilqrSolver._backward_pass  control.py:116-148  -> ProblemBatch.make_tiles + backward_pass_tiles
     ilqrSolver._forward_pass   control.py:95-114   -> ProblemBatch.forward_pass
     ilqrSolver.solve           control.py:150-225  -> ProblemBatch.solve
-    (no reference counterpart: the feedback policy closed loop)  -> ProblemBatch.policy_rollout
+    (no reference counterpart: the feedback policy closed loop)  -> ProblemBatch.policy_rollout, .policy_rollout_dec
 """
 import ctypes as C
 import os
@@ -317,6 +317,75 @@ class ProblemBatch:
         _lib.check(self._lib.dpilqr_policy_rollout(self._d, ptr(X), ptr(U), ptr(K), S, ptr(x0s), ptr(W), ptr(u_lim),
                                                    ptr(out.get("X")), ptr(out.get("U")), ptr(out["J"]), ptr(out["min_sep"]),
                                                    ptr(out["goal_dist"]), stream_handle()))
+        return out
+
+    def _policy_dec_shapes(self, X, U_ff, Kc, nbr_bits, x0s, W, u_lim, check_masks=True):
+        """Host-side validation of policy_rollout_dec's arguments: returns (samples per item, kc_max, the masks as a host
+        int64 array -- None with check_masks=False).  Only the masks are read, and only when they are a device tensor
+        (B * k words)."""
+        B, T, k, n, m, ns, nc = self.B, self.T, self.k, self.n_x, self.n_u, self.n_s, self.n_c
+        if n > 60 or k > 20:
+            raise ValueError(f"policy_rollout_dec serves clusters up to n_x = 60 and k = 20, this batch has n_x = {n}, k = {k}")
+        shape = lambda a: tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)
+        sk = shape(Kc)
+        if len(sk) != 5 or sk[:4] != (B, T, k, nc) or sk[4] < ns or sk[4] % ns or sk[4] > n:
+            raise ValueError(f"policy_rollout_dec: Kc has shape {sk}, expected ({B}, {T}, {k}, {nc}, kc_max * {ns}) with 1 <= kc_max <= {k}")
+        kc_max = sk[4] // ns
+        for name, a, want in (("X", X, (B, T + 1, n)), ("U_ff", U_ff, (B, T, m)), ("nbr_bits", nbr_bits, (B, k))):
+            if shape(a) != want:
+                raise ValueError(f"policy_rollout_dec: {name} has shape {shape(a)}, expected {want}")
+        sx = shape(x0s)
+        if len(sx) != 3 or sx[0] != B or sx[2] != n or sx[1] < 1:
+            raise ValueError(f"policy_rollout_dec: x0s has shape {sx}, expected ({B}, n_samples >= 1, {n})")
+        S = int(sx[1])
+        if W is not None and shape(W) != (B, S, T, n):
+            raise ValueError(f"policy_rollout_dec: W has shape {shape(W)}, expected {(B, S, T, n)}")
+        if u_lim is not None:
+            if shape(u_lim) != (2, m):
+                raise ValueError(f"policy_rollout_dec: u_lim has shape {shape(u_lim)}, expected {(2, m)} (lower row, upper row)")
+            lim = u_lim.cpu().numpy() if isinstance(u_lim, torch.Tensor) else np.asarray(u_lim, dtype=np.float64)
+            if not bool((lim[0] <= lim[1]).all()):
+                raise ValueError("policy_rollout_dec: u_lim has a lower limit above its upper limit")
+        if not check_masks:
+            return S, kc_max, None
+        # the masks: DPILQR_EINVAL of include/dpilqr_policy.h, decided here because the C entry point only enqueues
+        bits = nbr_bits.cpu().numpy() if isinstance(nbr_bits, torch.Tensor) else np.asarray(nbr_bits)
+        if bits.dtype.kind not in "iu":
+            raise ValueError(f"policy_rollout_dec: nbr_bits has dtype {bits.dtype}, expected integer bit masks")
+        bits = np.ascontiguousarray(bits.astype(np.uint64) & np.uint64((1 << k) - 1))
+        own = np.uint64(1) << np.arange(k, dtype=np.uint64)
+        if not bool(((bits & own[None, :]) != 0).all()):
+            raise ValueError("policy_rollout_dec: a neighbourhood mask lacks its agent's own bit (DPILQR_EINVAL)")
+        count = np.zeros((B, k), dtype=np.int64)
+        for j in range(k):
+            count += ((bits >> np.uint64(j)) & np.uint64(1)).astype(np.int64)
+        if int(count.max(initial=0)) > kc_max:
+            raise ValueError(f"policy_rollout_dec: a neighbourhood mask has {int(count.max())} members, Kc holds kc_max = {kc_max} "
+                             "(DPILQR_EINVAL)")
+        return S, kc_max, bits.view(np.int64)
+
+    def policy_rollout_dec(self, X, U_ff, Kc, nbr_bits, x0s, W=None, u_lim=None, trajectories=False, masks_checked=None):
+        """The closed loop of a distributed solution (dpilqr_policy_rollout_dec): agent i of item b applies
+        u_i = U_ff[b][t][i] + Kc[b][t][i] (x - X[b][t]) over its neighbourhood nbr_bits[b][i] only (bit j = agent j, its own bit
+        set).  X (B,T+1,n_x): the stitched trajectory; U_ff (B,T,n_u); Kc (B,T,k,n_c,kc_max*n_s): agent i's rows, the columns its
+        neighbourhood's members in ascending order (columns past them are never read); nbr_bits (B,k) integer masks;
+        x0s, W, u_lim, trajectories and the returned dict: as policy_rollout, on this (full k-agent) batch.
+        masks_checked: the very int64 device tensor given as nbr_bits, if an earlier call has already checked it -- that call's
+        read-back of the masks is then not repeated (DistributedPolicy.rollout in a loop)."""
+        trusted = masks_checked is not None and masks_checked is nbr_bits and isinstance(nbr_bits, torch.Tensor) and nbr_bits.dtype == torch.int64
+        S, kc_max, bits = self._policy_dec_shapes(X, U_ff, Kc, nbr_bits, x0s, W, u_lim, check_masks=not trusted)
+        B, T, k, n, m = self.B, self.T, self.k, self.n_x, self.n_u
+        X = self._in(X, (B, T + 1, n)); U_ff = self._in(U_ff, (B, T, m)); Kc = self._in(Kc, (B, T, k, self.n_c, kc_max * self.n_s))
+        bits = nbr_bits.contiguous() if trusted else torch.from_numpy(bits).to(device())
+        x0s = self._in(x0s, (B, S, n))
+        W = None if W is None else self._in(W, (B, S, T, n))
+        u_lim = None if u_lim is None else self._in(u_lim, (2, m))
+        out = dict(J=empty((B, S)), min_sep=empty((B, S)), goal_dist=empty((B, S, k)))
+        if trajectories:
+            out["X"] = empty((B, S, T + 1, n)); out["U"] = empty((B, S, T, m))
+        _lib.check(self._lib.dpilqr_policy_rollout_dec(self._d, ptr(X), ptr(U_ff), ptr(Kc), kc_max, ptr(bits), S, ptr(x0s), ptr(W),
+                                                       ptr(u_lim), ptr(out.get("X")), ptr(out.get("U")), ptr(out["J"]),
+                                                       ptr(out["min_sep"]), ptr(out["goal_dist"]), stream_handle()))
         return out
 
     def cost(self, x, u, terminal=False):

@@ -786,6 +786,22 @@ int32_t dpilqr_policy_rollout(const dpilqr_batch_desc* desc, const double* X, co
     return launch_policy_rollout(*desc, X, U, K, n_samples, x0s, W, u_lim, Xs, Us, J, min_sep, goal_dist, as_stream(stream));
 }
 
+int32_t dpilqr_policy_rollout_dec(const dpilqr_batch_desc* desc, const double* X, const double* U_ff, const double* Kc, int32_t kc_max,
+                                  const uint64_t* nbr_bits, int32_t n_samples, const double* x0s, const double* W, const double* u_lim,
+                                  double* Xs, double* Us, double* J, double* min_sep, double* goal_dist, void* stream) {
+    int32_t rc = check_desc(desc);
+    if (rc) return rc;
+    if (!X || !U_ff || !Kc || !nbr_bits || !x0s || !J) return fail(DPILQR_EINVAL, "policy_rollout_dec: NULL pointer");
+    if (n_samples <= 0) return fail(DPILQR_EINVAL, "policy_rollout_dec: n_samples=%d", n_samples);
+    const uintptr_t dbls = reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(U_ff) | reinterpret_cast<uintptr_t>(Kc) |
+                           reinterpret_cast<uintptr_t>(nbr_bits) | reinterpret_cast<uintptr_t>(x0s) | reinterpret_cast<uintptr_t>(W) |
+                           reinterpret_cast<uintptr_t>(u_lim) | reinterpret_cast<uintptr_t>(Xs) | reinterpret_cast<uintptr_t>(Us) |
+                           reinterpret_cast<uintptr_t>(J) | reinterpret_cast<uintptr_t>(min_sep) | reinterpret_cast<uintptr_t>(goal_dist);
+    if (dbls % alignof(double) != 0) return fail(DPILQR_EINVAL, "policy_rollout_dec: a device pointer is not aligned to its element type");
+    return launch_policy_rollout_dec(*desc, X, U_ff, Kc, kc_max, nbr_bits, n_samples, x0s, W, u_lim, Xs, Us, J, min_sep, goal_dist,
+                                     as_stream(stream));
+}
+
 int32_t dpilqr_alphas(double* alphas_host) {
     if (!alphas_host) return fail(DPILQR_EINVAL, "alphas: NULL pointer");
     alpha_table(alphas_host);

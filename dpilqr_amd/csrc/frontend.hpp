@@ -11,6 +11,8 @@
 //   k_bucket_sort     stable counting sort of the representatives by cluster size: one contiguous list per size
 //   k_gather_bucket   x0 / U0 / x_f (and, for heterogeneous teams, per-agent parameters) of one size's sub-problems
 //   k_stitch          the owners' columns of every solved sub-problem -> X_dec, U_dec
+//   k_stitch_policy   the owners' rows of every sub-problem's gains -> the compact gains Kc and the folded nominal U_ff of the
+//                     distributed feedback policy (policy_dec.hpp)
 //   k_pack_rows / k_scatter_rows   the same through one row per (scenario, agent): what a rank contributes to, and takes
 //                     from, the path's single all-gather when the sub-problems are sharded over GPUs
 #pragma once
@@ -187,6 +189,57 @@ static __global__ void k_stitch(int S, int k, int n_s, int n_c, int T, const uns
     for (int q = threadIdx.x; q < T * n_c; q += blockDim.x) {
         const int t = q / n_c, c = q - t * n_c;
         U_dec[((int64_t)s * T + t) * k * n_c + i * n_c + c] = Ub[(int64_t)t * kc * n_c + pos * n_c + c];
+    }
+}
+
+struct BucketGains {         // gains of a backward pass at every solved sub-problem: K[kc] is [count][T][kc*n_c][kc*n_s]
+    const double* K[kFrontMaxAgents + 1];
+};
+
+// The feedback policy of the distributed solution, per (scenario s, agent i) with neighbourhood C_i (kc members, i at rank pos)
+// and sub-problem solution (X^i, U^i, K^i), kw = kc_max * n_s:
+//   Kc[s][t][i][c][col]   = K^i[t][pos*n_c + c][col] for col < kc*n_s (the columns are C_i's members in ascending order), else 0
+//   U_ff[s][t][i*n_c + c] = U^i[t][pos*n_c + c] + sum_col K^i[t][pos*n_c + c][col] (X_dec[s][t][C_i(col)] - X^i[t][col])
+// the sum over the columns in ascending order, one multiply and one add per term: u_i = U_ff_i + Kc_i (x_{C_i} - X_dec_{C_i})
+// is then u_i = U^i_i + K^i_i (x_{C_i} - X^i), and where C_i is the whole scenario X_dec = X^i and U_ff = U_dec exactly.
+// X_dec: the stitched trajectories (k_stitch has run).
+static __global__ void k_stitch_policy(int S, int k, int n_s, int n_c, int T, int kc_max, const unsigned long long* __restrict__ bits,
+                                       const int32_t* __restrict__ rep, const int32_t* __restrict__ size,
+                                       const int32_t* __restrict__ slot, BucketResults R, BucketGains G,
+                                       const double* __restrict__ X_dec, double* __restrict__ Kc, double* __restrict__ U_ff) {
+    const int64_t e = blockIdx.x;             // (s, i)
+    if (e >= (int64_t)S * k) return;
+    int kc, sl, pos;
+    if (!owner_lookup(k, bits, rep, size, slot, e, kc, sl, pos)) return;
+    sl -= R.first[kc];
+    if (sl < 0 || sl >= R.count[kc] || kc > kc_max) return;
+    const int s = (int)(e / k), i = (int)(e % k);
+    const unsigned long long m = bits[e];
+    __shared__ int mem[kFrontMaxAgents];
+    if (threadIdx.x == 0) {
+        int p = 0;
+        for (int a = 0; a < k; ++a)
+            if ((m >> a) & 1ull) mem[p++] = a;
+    }
+    __syncthreads();
+    const int nx = kc * n_s, nu = kc * n_c, kw = kc_max * n_s;
+    const double* Xb = R.X[kc] + (int64_t)sl * (T + 1) * nx;
+    const double* Ub = R.U[kc] + (int64_t)sl * T * nu;
+    const double* Kb = G.K[kc] + (int64_t)sl * T * nu * nx;
+    for (int q = threadIdx.x; q < T * n_c * kw; q += blockDim.x) {
+        const int t = q / (n_c * kw), r = q - t * n_c * kw, c = r / kw, col = r - c * kw;
+        Kc[(((int64_t)s * T + t) * k + i) * n_c * kw + r] = col < nx ? Kb[((int64_t)t * nu + pos * n_c + c) * nx + col] : 0.0;
+    }
+    for (int q = threadIdx.x; q < T * n_c; q += blockDim.x) {
+        const int t = q / n_c, c = q - t * n_c;
+        const double* Krow = Kb + ((int64_t)t * nu + pos * n_c + c) * nx;
+        const double* Xd = X_dec + ((int64_t)s * (T + 1) + t) * k * n_s;
+        double sum = 0.0;
+        for (int col = 0; col < nx; ++col) {
+            const int p = col / n_s;
+            sum += Krow[col] * (Xd[mem[p] * n_s + (col - p * n_s)] - Xb[(int64_t)t * nx + col]);
+        }
+        U_ff[((int64_t)s * T + t) * k * n_c + i * n_c + c] = Ub[(int64_t)t * nu + pos * n_c + c] + sum;
     }
 }
 

@@ -5,7 +5,7 @@
 // batched entry points), tu_big.hip (the sweep for n_x > 60 and the fp32 arm), tu_bigfwd.hip (their forward passes),
 // tu_team.hip (the fused wavefront sweeps with a helper wavefront per item), tu_inprod.hip (the wavefront sweeps with in-sweep
 // production), tu_bike.hip (the same for the five-state family, BikeDynamics5D), tu_lsteam.hip (the line search with two
-// wavefronts per item), tu_frontend.hip (the device-side dispatch front / back end), tu_policy.hip (the closed-loop ensemble rollout) and
+// wavefronts per item), tu_frontend.hip (the device-side dispatch front / back end), tu_policy.hip (the closed-loop ensemble rollouts) and
 // dpilqr_hip.hip (the C ABI and the solve loop).
 // No device code crosses a file boundary.
 #pragma once
@@ -214,6 +214,10 @@ int32_t launch_pairwise_graph(int32_t S, int32_t N, int32_t k, int32_t n_s, cons
 int32_t launch_policy_rollout(const dpilqr_batch_desc& D, const double* X, const double* U, const double* K, int32_t n_samples,
                               const double* x0s, const double* W, const double* u_lim, double* Xs, double* Us, double* J,
                               double* min_sep, double* goal_dist, hipStream_t st);
+// ... and of a distributed solution: u_i = U_ff_i + Kc_i (x - X_dec) over agent i's neighbourhood nbr_bits[b][i] (policy_dec.hpp)
+int32_t launch_policy_rollout_dec(const dpilqr_batch_desc& D, const double* X, const double* U_ff, const double* Kc, int32_t kc_max,
+                                  const uint64_t* nbr_bits, int32_t n_samples, const double* x0s, const double* W, const double* u_lim,
+                                  double* Xs, double* Us, double* J, double* min_sep, double* goal_dist, hipStream_t st);
 
 // ---- tu_big.hip: large clusters (n_x > 60) in fp64, any size in fp32 (BASELINE config 5's tolerance study)
 int64_t riccati_big_scratch_elems(int n, int m);   // per sub-problem in flight, in elements of the arithmetic type

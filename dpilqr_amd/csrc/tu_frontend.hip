@@ -10,6 +10,7 @@
 using namespace dpilqr;
 
 static_assert(sizeof(dpilqr_bucket_results) == sizeof(BucketResults), "dpilqr_bucket_results mirrors BucketResults");
+static_assert(sizeof(dpilqr_bucket_gains) == sizeof(BucketGains), "dpilqr_bucket_gains mirrors BucketGains");
 static_assert(DPILQR_MAX_AGENTS == kFrontMaxAgents, "one bit per agent");
 
 namespace {
@@ -89,6 +90,28 @@ int32_t dpilqr_dispatch_stitch(int32_t S, int32_t k, int32_t n_s, int32_t n_c, i
     if (S == 0) return DPILQR_OK;
     hipLaunchKernelGGL(k_stitch, dim3((unsigned)((int64_t)S * k)), dim3(128), 0, as_stream(stream), S, k, n_s, n_c, T,
                        reinterpret_cast<const unsigned long long*>(bits), rep, size, slot, to_internal(results), X_dec, U_dec);
+    HIP_TRY(hipGetLastError());
+    return DPILQR_OK;
+}
+
+int32_t dpilqr_dispatch_stitch_policy(int32_t S, int32_t k, int32_t n_s, int32_t n_c, int32_t T, int32_t kc_max, const uint64_t* bits,
+                                      const int32_t* rep, const int32_t* size, const int32_t* slot,
+                                      const dpilqr_bucket_results* results, const dpilqr_bucket_gains* gains, const double* X_dec,
+                                      double* Kc, double* U_ff, void* stream) {
+    if (S < 0 || k < 1 || k > kFrontMaxAgents || n_s < 1 || n_c < 1 || T < 1 || !bits || !rep || !size || !slot || !results || !gains ||
+        !X_dec || !Kc || !U_ff)
+        return fail(DPILQR_EINVAL, "dispatch_stitch_policy: bad argument");
+    if (kc_max < 1 || kc_max > k) return fail(DPILQR_EINVAL, "dispatch_stitch_policy: kc_max=%d, a neighbourhood has 1 .. k = %d members", kc_max, k);
+    for (int kc = 1; kc <= k; ++kc) {
+        if (results->count[kc] <= 0) continue;
+        if (kc > kc_max) return fail(DPILQR_EINVAL, "dispatch_stitch_policy: sub-problems of %d agents, kc_max=%d", kc, kc_max);
+        if (!results->X[kc] || !results->U[kc] || !gains->K[kc]) return fail(DPILQR_EINVAL, "dispatch_stitch_policy: NULL results of size %d", kc);
+    }
+    if (S == 0) return DPILQR_OK;
+    BucketGains G;
+    memcpy(&G, gains, sizeof(G));
+    hipLaunchKernelGGL(k_stitch_policy, dim3((unsigned)((int64_t)S * k)), dim3(128), 0, as_stream(stream), S, k, n_s, n_c, T, kc_max,
+                       reinterpret_cast<const unsigned long long*>(bits), rep, size, slot, to_internal(results), G, X_dec, Kc, U_ff);
     HIP_TRY(hipGetLastError());
     return DPILQR_OK;
 }

@@ -199,6 +199,23 @@ class ScenarioFrontEnd:
                                                    C.addressof(R), ptr(X_dec), ptr(U_dec), stream_handle()))
         return X_dec, U_dec
 
+    def stitch_policy(self, solved, gains, X_dec):
+        """The distributed feedback policy (dpilqr_dispatch_stitch_policy): solved as for stitch, gains {kc: K} the bucket's
+        backward-pass gains (count, T, kc*n_c, kc*n_s), X_dec the stitched trajectories -> Kc (S, T, k, n_c, kc_max*n_s),
+        U_ff (S, T, k*n_c), kc_max (the largest populated cluster size)."""
+        import ctypes as C
+        S, k, ns, nc, T = self.S, self.k, self.n_s, self.n_c, self.T
+        kc_max = max(self.sizes(), default=1)
+        Kc = empty((S, T, k, nc, kc_max * ns)); U_ff = empty((S, T, k * nc))
+        R = self.results_struct(solved)
+        G = _lib.BucketGains()
+        for kc, K in gains.items():
+            G.K[kc] = K.data_ptr()
+        _lib.check(self.lib.dpilqr_dispatch_stitch_policy(S, k, ns, nc, T, kc_max, ptr(self.bits), ptr(self.rep), ptr(self.size),
+                                                          ptr(self.slot), C.addressof(R), C.addressof(G), ptr(X_dec), ptr(Kc),
+                                                          ptr(U_ff), stream_handle()))
+        return Kc, U_ff, kc_max
+
     def pack_rows(self, solved, count_only=False, pad_to=None):
         """One row [s*k+i | X columns | U columns] per (scenario, agent) whose sub-problem is in `solved`; returns
         (rows or None, n_rows).  Rows beyond n_rows (up to pad_to) carry index -1."""
@@ -224,8 +241,43 @@ class ScenarioFrontEnd:
         return X_dec, U_dec
 
 
+class DistributedPolicy:
+    """The feedback policy of a distributed solution of S scenarios, on the device (solve_scenarios_distributed(policy=True)):
+    agent i of scenario s applies u_i = U_ff[s][t][i] + Kc[s][t][i] (x - X_dec[s][t]) over its neighbourhood bits[s][i].
+    X_dec (S,T+1,n_x), U_ff (S,T,n_u), Kc (S,T,k,n_c,kc_max*n_s), bits (S,k) int64 masks, kc_max; desc: the problem's
+    description (lowering.describe), xf (S,n_x) the scenarios' goals."""
+
+    def __init__(self, desc, xf, X_dec, U_ff, Kc, bits, kc_max):
+        self.desc, self.xf, self.X_dec, self.U_ff, self.Kc, self.bits, self.kc_max = desc, xf, X_dec, U_ff, Kc, bits, int(kc_max)
+        self._batch = self._masks_checked = None
+
+    def batch(self):
+        """The full k-agent problem of every scenario, as full_rollout_cost builds it; made once."""
+        if self._batch is None:
+            d, S, T = self.desc, int(self.X_dec.shape[0]), int(self.U_ff.shape[1])
+            k = d["k"]
+            c = device_constants(d)
+            self._batch = ProblemBatch(c["model"], c["n_dims"], self.xf, c["Q"], c["R"], c["Qf"], d["radius"], d["dt"], T,
+                                       w_ref=d["w_ref"], w_prox=d["w_prox"], B=S,
+                                       hints=(k, int(self.X_dec.shape[2]) // k, int(self.U_ff.shape[2]) // k, c["word"]))
+        return self._batch
+
+    def rollout(self, x0s, W=None, u_lim=None, trajectories=False):
+        """x0s (S, n_samples, n_x) starts per scenario; W (S, n_samples, T, n_x) or None; u_lim (2, n_u) or None.  Returns device
+        tensors J, min_sep (S, n_samples), goal_dist (S, n_samples, k) and, with trajectories=True, X, U
+        (ProblemBatch.policy_rollout_dec on the full problem).  The masks are read back and checked by the first call only."""
+        shape = tuple(x0s.shape) if isinstance(x0s, torch.Tensor) else np.shape(x0s)
+        S, n = int(self.X_dec.shape[0]), int(self.X_dec.shape[2])
+        if len(shape) != 3 or shape[0] != S or shape[2] != n or shape[1] < 1:
+            raise ValueError(f"DistributedPolicy.rollout: x0s has shape {shape}, expected ({S}, n_samples >= 1, {n})")
+        r = self.batch().policy_rollout_dec(self.X_dec, self.U_ff, self.Kc, self.bits, x0s, W=W, u_lim=u_lim,
+                                            trajectories=trajectories, masks_checked=self._masks_checked)
+        self._masks_checked = self.bits
+        return r
+
+
 def solve_scenarios_distributed(problem, X, U, radius, xf=None, window=None, concurrent=True, ignore_ids=None, device_out=False,
-                                shard=None, audit=False, desc=None, **kwargs):
+                                shard=None, audit=False, desc=None, policy=False, policy_mu=0.0, **kwargs):
     """solve_distributed (distributed.py:25-103) for S scenarios of ONE k-agent problem at once -- the Monte-Carlo
     front end (scripts/analysis.py:126-174 runs it seed by seed).  Everything between the trajectories and the stitched
     result stays on the device: graph, de-duplication, size buckets, gathered sub-problem inputs (ScenarioFrontEnd), one
@@ -237,11 +289,17 @@ def solve_scenarios_distributed(problem, X, U, radius, xf=None, window=None, con
     shard = (rank, world): solve only this rank's share of every size bucket (sharding.solve_scenarios_sharded)
     audit : keep every bucket's sub-problem inputs and full solve record (x0, xf, U0, X, U, J, status, n_bwd, n_fwd and the
             decision trace) as host arrays in info["audit"][cluster size] -- what a parity check of the individual
-            sub-problem solves needs; the solves themselves are the same
+            sub-problem solves needs; the solves themselves are the same (with policy=True also the bucket's gains K)
+    policy: also take the feedback policy of the distributed solution -- one backward pass per bucket at its solved (X, U) with
+            regularisation policy_mu (ilqrSolver.closed_loop takes its gains the same way), stitched on the device into
+            info["policy"], a DistributedPolicy; not with `shard` or `ignore_ids`
     returns X_dec (S, T+1, n_x), U_dec (S, T, n_u), J_full (S,), info (clusters as bit masks, counts) -- NumPy arrays, or
     device tensors with device_out=True; with `shard` the unstitched (front end, solved slices) pair instead.
     """
     from .sharding import shard_bounds
+    if policy and (shard is not None or ignore_ids):
+        raise ValueError("solve_scenarios_distributed: policy=True serves neither shard= nor ignore_ids (every agent of every "
+                         "scenario needs its sub-problem's gains on this device)")
     d = desc if desc is not None else describe(problem)      # desc: the caller's description (its device constants are reused)
     k = d["k"]
     ignore = None
@@ -268,12 +326,15 @@ def solve_scenarios_distributed(problem, X, U, radius, xf=None, window=None, con
         with torch.cuda.device(dev_index), torch.cuda.stream(torch.cuda.Stream(device=dev_index)):
             pb, x0, U0 = fe.bucket(kc, lo, hi)
             r = pb.solve(x0, U0, window=window, trace=bool(audit), **solve_kw)
+            K = pb.backward_pass(r["X"], r["U"], float(policy_mu))[0] if policy else None
             torch.cuda.current_stream().synchronize()
             rec = None
             if audit:
                 rec = {key: v.cpu().numpy() for key, v in r.items()}
                 rec.update(x0=x0.cpu().numpy(), U0=U0.cpu().numpy(), xf=pb._xf.cpu().numpy().reshape(hi - lo, -1), lo=lo)
-            return kc, (r["X"], r["U"], lo, hi - lo, int(r["n_bwd"].sum().item()), rec)
+                if policy:
+                    rec["K"] = K.cpu().numpy()
+            return kc, (r["X"], r["U"], lo, hi - lo, int(r["n_bwd"].sum().item()), rec, K)
 
     # buckets are independent and, for a handful of scenarios, small: their solves run concurrently, each on its own
     # HIP stream from its own host thread
@@ -300,6 +361,12 @@ def solve_scenarios_distributed(problem, X, U, radius, xf=None, window=None, con
     J = full_rollout_cost(d, fe, U_dec)
     torch.cuda.synchronize()
     info["seconds"]["stitch_and_rollout"] = pc() - t0
+    if policy:
+        t0 = pc()
+        Kc, U_ff, kc_max = fe.stitch_policy(solved, {kc: r[6] for kc, r in results if r is not None}, X_dec)
+        torch.cuda.synchronize()
+        info["seconds"]["stitch_policy"] = pc() - t0
+        info["policy"] = DistributedPolicy(d, fe.xf, X_dec, U_ff, Kc, fe.bits.reshape(S, k), kc_max)
     info["cluster_bits"] = fe.bits.cpu().numpy().reshape(S, k)
     if device_out:
         return X_dec, U_dec, J, info

@@ -202,10 +202,11 @@ int32_t dpilqr_backward_pass_fused(const dpilqr_batch_desc* desc, const double* 
 int32_t dpilqr_forward_pass(const dpilqr_batch_desc* desc, const double* X, const double* U, const double* K,
                             const double* d, const double* alphas, int32_t n_alpha, double* Xn, double* Un,
                             double* Jn, void* stream);
-/* -------------------------------------------------- (4b) the closed-loop ensemble rollout: dpilqr_policy_rollout
- * An additive entry point (the ABI version stays): declared, with its semantics, in the extension header below, which is part
- * of this header for every includer.  The identical-ABI CPU twin of the test suite covers the symbols named in this file. */
-#include "dpilqr_policy.h"
+/* -------------------------------------------------- (4b) the closed-loop ensemble rollouts: dpilqr_policy_rollout,
+ * dpilqr_policy_rollout_dec and the stitch of a distributed solution's policy, dpilqr_dispatch_stitch_policy
+ * Additive entry points (the ABI version stays): declared, with their semantics, in the extension header dpilqr_policy.h, which
+ * is part of this header for every includer (included at its end, after the types of section 7).  The identical-ABI CPU twin of
+ * the test suite covers the symbols named in this file. */
 
 /* the float32-rounded line-search table of control.py:162 (host array of DPILQR_N_ALPHA doubles) */
 int32_t dpilqr_alphas(double* alphas_host);
@@ -369,6 +370,8 @@ int32_t dpilqr_dispatch_scatter_rows(int64_t n_rows_total, int32_t k, int32_t n_
  * orders -- so that a Monte-Carlo driver needs neither a host loop over seeds nor an upload.  energy = 0: no normalisation. */
 int32_t dpilqr_random_setup(int32_t S, int64_t seed0, int32_t k, int32_t n_s, int32_t n_d, double var, double energy,
                             double* x0, double* xf, void* stream);
+
+#include "dpilqr_policy.h"
 
 #ifdef __cplusplus
 }

@@ -36,4 +36,41 @@ int32_t dpilqr_policy_rollout(const dpilqr_batch_desc* desc, const double* X, co
                               int32_t n_samples, const double* x0s, const double* W, const double* u_lim, double* Xs,
                               double* Us, double* J, double* min_sep, double* goal_dist, void* stream);
 
+/* The closed loop of a DISTRIBUTED solution (dpilqr_dispatch_* of dpilqr_hip.h): every agent runs the feedback law of the
+ * sub-problem solved for its own neighbourhood.  Agent i of item b has the neighbourhood mask nbr_bits[b][i] (bit j = agent j;
+ * bit i set; the masks need not be symmetric), C_i its members in ascending order, kc_i their number, kw = kc_max * n_s.
+ * Per (item b, sample s), with the steps, limits, disturbance and results of dpilqr_policy_rollout on the FULL k-agent problem
+ * of `desc` (all pairs in combinations order, quirk Q5):
+ *     u_i(t) = U_ff[b][t][i] + sum_col Kc[b][t][i][.][col] (x_{C_i}(t) - X[b][t]_{C_i})[col]     col = 0 .. kc_i * n_s - 1, ascending
+ * X[B][T+1][n_x]: the stitched trajectory X_dec; U_ff[B][T][n_u]; Kc[B][T][k][n_c][kw] compact gains: agent i's n_c rows, the
+ * columns C_i's members in ascending order.  Columns at and past kc_i * n_s are never read (they may hold anything, NaN included).
+ * Limits: fp64, n_x <= 60, k <= 20, 1 <= kc_max <= k; DPILQR_EUNSUPPORTED beyond, before any launch.
+ * The caller's contract, NOT checked here (the masks are device memory and this call only enqueues): every mask has its own
+ * bit and at most kc_max bits among the low k.  A mask that breaks it makes that agent's controls meaningless (members past
+ * the kc_max-th are dropped); no memory outside the arguments is touched.  The Python wrapper checks the masks on the host and answers DPILQR_EINVAL.
+ * Enqueue only, nothing is allocated.  The kernel reads k n_c kw doubles of gains per step and workgroup where the dense form
+ * reads n_u n_x (csrc/policy_dec.hpp). */
+int32_t dpilqr_policy_rollout_dec(const dpilqr_batch_desc* desc, const double* X, const double* U_ff, const double* Kc,
+                                  int32_t kc_max, const uint64_t* nbr_bits, int32_t n_samples, const double* x0s, const double* W,
+                                  const double* u_lim, double* Xs, double* Us, double* J, double* min_sep, double* goal_dist,
+                                  void* stream);
+
+/* Gains of the solved sub-problems, per cluster size kc, beside dpilqr_bucket_results (same slices [first, first + count)):
+ * K[kc] is [count][T][kc*n_c][kc*n_s], a backward pass at that bucket's (X, U). */
+typedef struct dpilqr_bucket_gains {
+    const double* K[DPILQR_MAX_AGENTS + 1];
+} dpilqr_bucket_gains;
+
+/* The stitch of the distributed policy, after dpilqr_dispatch_stitch has filled X_dec: for every (scenario s, agent i) whose
+ * sub-problem (neighbourhood C_i of kc members, i at rank pos, solution X^i, U^i, gains K^i) is among `results`,
+ *     Kc[s][t][i][c][col]   = K^i[t][pos*n_c + c][col]   for col < kc*n_s, 0 for kc*n_s <= col < kc_max*n_s
+ *     U_ff[s][t][i*n_c + c] = U^i[t][pos*n_c + c] + sum_col K^i[t][pos*n_c + c][col] (X_dec[s][t]_{C_i}[col] - X^i[t][col])
+ * (columns ascending, one multiply and one add per term): the nominal of dpilqr_policy_rollout_dec, for which
+ * u_i = U^i_i + K^i_i (x_{C_i} - X^i).  Where C_i is the whole scenario U_ff equals U_dec.  kc_max: at least the largest
+ * populated cluster size (DPILQR_EINVAL otherwise).  Kc[S][T][k][n_c][kc_max*n_s], U_ff[S][T][k*n_c].  Enqueue only. */
+int32_t dpilqr_dispatch_stitch_policy(int32_t S, int32_t k, int32_t n_s, int32_t n_c, int32_t T, int32_t kc_max, const uint64_t* bits,
+                                      const int32_t* rep, const int32_t* size, const int32_t* slot,
+                                      const dpilqr_bucket_results* results, const dpilqr_bucket_gains* gains, const double* X_dec,
+                                      double* Kc, double* U_ff, void* stream);
+
 #endif /* DPILQR_POLICY_H */
