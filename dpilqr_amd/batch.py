@@ -276,28 +276,46 @@ class ProblemBatch:
         _lib.check(fn(self._d, ptr(X), ptr(U), ptr(K), ptr(d), ptr(al), A, ptr(Xn), ptr(Un), ptr(Jn), stream_handle()))
         return Xn, Un, Jn
 
+    def _policy_common(self, who, X, x0s, W, u_lim, others):
+        """Host-side validation of what policy_rollout and policy_rollout_dec share (no device access): X, x0s, W, u_lim and
+        `others` -- (name, array, shape) of the caller's further arrays --; `who` is the caller's name in the messages.  Returns
+        the number of samples per item."""
+        B, T, n, m = self.B, self.T, self.n_x, self.n_u
+        shape = lambda a: tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)
+        for name, a, want in (("X", X, (B, T + 1, n)),) + tuple(others):
+            if shape(a) != want:
+                raise ValueError(f"{who}: {name} has shape {shape(a)}, expected {want}")
+        sx = shape(x0s)
+        if len(sx) != 3 or sx[0] != B or sx[2] != n or sx[1] < 1:
+            raise ValueError(f"{who}: x0s has shape {sx}, expected ({B}, n_samples >= 1, {n})")
+        S = int(sx[1])
+        if W is not None and shape(W) != (B, S, T, n):
+            raise ValueError(f"{who}: W has shape {shape(W)}, expected {(B, S, T, n)}")
+        if u_lim is not None:
+            if shape(u_lim) != (2, m):
+                raise ValueError(f"{who}: u_lim has shape {shape(u_lim)}, expected {(2, m)} (lower row, upper row)")
+            lim = u_lim.cpu().numpy() if isinstance(u_lim, torch.Tensor) else np.asarray(u_lim, dtype=np.float64)
+            if not bool((lim[0] <= lim[1]).all()):
+                raise ValueError(f"{who}: u_lim has a lower limit above its upper limit")
+        return S
+
+    def _policy_stage(self, S, X, U, x0s, W, u_lim, trajectories):
+        """The inputs both rollouts share on the device, and the dict of their outputs."""
+        B, T, n, m = self.B, self.T, self.n_x, self.n_u
+        X = self._in(X, (B, T + 1, n)); U = self._in(U, (B, T, m)); x0s = self._in(x0s, (B, S, n))
+        W = None if W is None else self._in(W, (B, S, T, n))
+        u_lim = None if u_lim is None else self._in(u_lim, (2, m))
+        out = dict(J=empty((B, S)), min_sep=empty((B, S)), goal_dist=empty((B, S, self.k)))
+        if trajectories:
+            out["X"] = empty((B, S, T + 1, n)); out["U"] = empty((B, S, T, m))
+        return X, U, x0s, W, u_lim, out
+
     def _policy_shapes(self, X, U, K, x0s, W, u_lim):
         """Host-side validation of policy_rollout's arguments (no device access): returns the number of samples per item."""
         B, T, n, m = self.B, self.T, self.n_x, self.n_u
         if n > 60:
             raise ValueError(f"policy_rollout serves clusters up to n_x = 60, this batch has n_x = {n}")
-        shape = lambda a: tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)
-        for name, a, want in (("X", X, (B, T + 1, n)), ("U", U, (B, T, m)), ("K", K, (B, T, m, n))):
-            if shape(a) != want:
-                raise ValueError(f"policy_rollout: {name} has shape {shape(a)}, expected {want}")
-        sx = shape(x0s)
-        if len(sx) != 3 or sx[0] != B or sx[2] != n or sx[1] < 1:
-            raise ValueError(f"policy_rollout: x0s has shape {sx}, expected ({B}, n_samples >= 1, {n})")
-        S = int(sx[1])
-        if W is not None and shape(W) != (B, S, T, n):
-            raise ValueError(f"policy_rollout: W has shape {shape(W)}, expected {(B, S, T, n)}")
-        if u_lim is not None:
-            if shape(u_lim) != (2, m):
-                raise ValueError(f"policy_rollout: u_lim has shape {shape(u_lim)}, expected {(2, m)} (lower row, upper row)")
-            lim = u_lim.cpu().numpy() if isinstance(u_lim, torch.Tensor) else np.asarray(u_lim, dtype=np.float64)
-            if not bool((lim[0] <= lim[1]).all()):
-                raise ValueError("policy_rollout: u_lim has a lower limit above its upper limit")
-        return S
+        return self._policy_common("policy_rollout", X, x0s, W, u_lim, (("U", U, (B, T, m)), ("K", K, (B, T, m, n))))
 
     def policy_rollout(self, X, U, K, x0s, W=None, u_lim=None, trajectories=False):
         """The closed-loop ensemble rollout (dpilqr_policy_rollout): every item's feedback policy u_t = U[t] + K[t] (x_t - X[t])
@@ -306,14 +324,8 @@ class ProblemBatch:
         limits shared by all items or None.  Returns a dict of device tensors: J (B,S), min_sep (B,S), goal_dist (B,S,k) and,
         with trajectories=True, X (B,S,T+1,n_x), U (B,S,T,n_u)."""
         S = self._policy_shapes(X, U, K, x0s, W, u_lim)
-        B, T, n, m = self.B, self.T, self.n_x, self.n_u
-        X = self._in(X, (B, T + 1, n)); U = self._in(U, (B, T, m)); K = self._in(K, (B, T, m, n))
-        x0s = self._in(x0s, (B, S, n))
-        W = None if W is None else self._in(W, (B, S, T, n))
-        u_lim = None if u_lim is None else self._in(u_lim, (2, m))
-        out = dict(J=empty((B, S)), min_sep=empty((B, S)), goal_dist=empty((B, S, self.k)))
-        if trajectories:
-            out["X"] = empty((B, S, T + 1, n)); out["U"] = empty((B, S, T, m))
+        X, U, x0s, W, u_lim, out = self._policy_stage(S, X, U, x0s, W, u_lim, trajectories)
+        K = self._in(K, (self.B, self.T, self.n_u, self.n_x))
         _lib.check(self._lib.dpilqr_policy_rollout(self._d, ptr(X), ptr(U), ptr(K), S, ptr(x0s), ptr(W), ptr(u_lim),
                                                    ptr(out.get("X")), ptr(out.get("U")), ptr(out["J"]), ptr(out["min_sep"]),
                                                    ptr(out["goal_dist"]), stream_handle()))
@@ -326,26 +338,11 @@ class ProblemBatch:
         B, T, k, n, m, ns, nc = self.B, self.T, self.k, self.n_x, self.n_u, self.n_s, self.n_c
         if n > 60 or k > 20:
             raise ValueError(f"policy_rollout_dec serves clusters up to n_x = 60 and k = 20, this batch has n_x = {n}, k = {k}")
-        shape = lambda a: tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)
-        sk = shape(Kc)
+        sk = tuple(Kc.shape) if isinstance(Kc, torch.Tensor) else np.shape(Kc)
         if len(sk) != 5 or sk[:4] != (B, T, k, nc) or sk[4] < ns or sk[4] % ns or sk[4] > n:
             raise ValueError(f"policy_rollout_dec: Kc has shape {sk}, expected ({B}, {T}, {k}, {nc}, kc_max * {ns}) with 1 <= kc_max <= {k}")
         kc_max = sk[4] // ns
-        for name, a, want in (("X", X, (B, T + 1, n)), ("U_ff", U_ff, (B, T, m)), ("nbr_bits", nbr_bits, (B, k))):
-            if shape(a) != want:
-                raise ValueError(f"policy_rollout_dec: {name} has shape {shape(a)}, expected {want}")
-        sx = shape(x0s)
-        if len(sx) != 3 or sx[0] != B or sx[2] != n or sx[1] < 1:
-            raise ValueError(f"policy_rollout_dec: x0s has shape {sx}, expected ({B}, n_samples >= 1, {n})")
-        S = int(sx[1])
-        if W is not None and shape(W) != (B, S, T, n):
-            raise ValueError(f"policy_rollout_dec: W has shape {shape(W)}, expected {(B, S, T, n)}")
-        if u_lim is not None:
-            if shape(u_lim) != (2, m):
-                raise ValueError(f"policy_rollout_dec: u_lim has shape {shape(u_lim)}, expected {(2, m)} (lower row, upper row)")
-            lim = u_lim.cpu().numpy() if isinstance(u_lim, torch.Tensor) else np.asarray(u_lim, dtype=np.float64)
-            if not bool((lim[0] <= lim[1]).all()):
-                raise ValueError("policy_rollout_dec: u_lim has a lower limit above its upper limit")
+        S = self._policy_common("policy_rollout_dec", X, x0s, W, u_lim, (("U_ff", U_ff, (B, T, m)), ("nbr_bits", nbr_bits, (B, k))))
         if not check_masks:
             return S, kc_max, None
         # the masks: DPILQR_EINVAL of include/dpilqr_policy.h, decided here because the C entry point only enqueues
@@ -374,15 +371,9 @@ class ProblemBatch:
         read-back of the masks is then not repeated (DistributedPolicy.rollout in a loop)."""
         trusted = masks_checked is not None and masks_checked is nbr_bits and isinstance(nbr_bits, torch.Tensor) and nbr_bits.dtype == torch.int64
         S, kc_max, bits = self._policy_dec_shapes(X, U_ff, Kc, nbr_bits, x0s, W, u_lim, check_masks=not trusted)
-        B, T, k, n, m = self.B, self.T, self.k, self.n_x, self.n_u
-        X = self._in(X, (B, T + 1, n)); U_ff = self._in(U_ff, (B, T, m)); Kc = self._in(Kc, (B, T, k, self.n_c, kc_max * self.n_s))
+        X, U_ff, x0s, W, u_lim, out = self._policy_stage(S, X, U_ff, x0s, W, u_lim, trajectories)
+        Kc = self._in(Kc, (self.B, self.T, self.k, self.n_c, kc_max * self.n_s))
         bits = nbr_bits.contiguous() if trusted else torch.from_numpy(bits).to(device())
-        x0s = self._in(x0s, (B, S, n))
-        W = None if W is None else self._in(W, (B, S, T, n))
-        u_lim = None if u_lim is None else self._in(u_lim, (2, m))
-        out = dict(J=empty((B, S)), min_sep=empty((B, S)), goal_dist=empty((B, S, k)))
-        if trajectories:
-            out["X"] = empty((B, S, T + 1, n)); out["U"] = empty((B, S, T, m))
         _lib.check(self._lib.dpilqr_policy_rollout_dec(self._d, ptr(X), ptr(U_ff), ptr(Kc), kc_max, ptr(bits), S, ptr(x0s), ptr(W),
                                                        ptr(u_lim), ptr(out.get("X")), ptr(out.get("U")), ptr(out["J"]),
                                                        ptr(out["min_sep"]), ptr(out["goal_dist"]), stream_handle()))

@@ -770,34 +770,34 @@ int32_t dpilqr_forward_pass(const dpilqr_batch_desc* desc, const double* X, cons
                           n_alpha, Xn, Un, Jn, S, nullptr, nullptr, desc->B, as_stream(stream));
 }
 
+// the argument checks the two closed-loop rollouts share, under the caller's name (W ... goal_dist may be null)
+static int32_t check_policy_args(const char* who, const dpilqr_batch_desc* desc, int32_t n_samples, const double* X, const double* U,
+                                 const double* K, const double* x0s, const double* J, const double* W, const double* u_lim,
+                                 const double* Xs, const double* Us, const double* min_sep, const double* goal_dist) {
+    const int32_t rc = check_desc(desc);
+    if (rc) return rc;
+    if (!X || !U || !K || !x0s || !J) return fail(DPILQR_EINVAL, "%s: NULL pointer", who);
+    if (n_samples <= 0) return fail(DPILQR_EINVAL, "%s: n_samples=%d", who, n_samples);
+    // the same alignment rule as the descriptor's pointers: a kernel reading a misaligned one faults the device
+    uintptr_t dbls = 0;
+    for (const double* p : {X, U, K, x0s, J, W, u_lim, Xs, Us, min_sep, goal_dist}) dbls |= reinterpret_cast<uintptr_t>(p);
+    return dbls % alignof(double) == 0 ? DPILQR_OK : fail(DPILQR_EINVAL, "%s: a device pointer is not aligned to its element type", who);
+}
+
 int32_t dpilqr_policy_rollout(const dpilqr_batch_desc* desc, const double* X, const double* U, const double* K, int32_t n_samples,
                               const double* x0s, const double* W, const double* u_lim, double* Xs, double* Us, double* J,
                               double* min_sep, double* goal_dist, void* stream) {
-    int32_t rc = check_desc(desc);
-    if (rc) return rc;
-    if (!X || !U || !K || !x0s || !J) return fail(DPILQR_EINVAL, "policy_rollout: NULL pointer");
-    if (n_samples <= 0) return fail(DPILQR_EINVAL, "policy_rollout: n_samples=%d", n_samples);
-    // the same alignment rule as the descriptor's pointers: a kernel reading a misaligned one faults the device
-    const uintptr_t dbls = reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(U) | reinterpret_cast<uintptr_t>(K) |
-                           reinterpret_cast<uintptr_t>(x0s) | reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(u_lim) |
-                           reinterpret_cast<uintptr_t>(Xs) | reinterpret_cast<uintptr_t>(Us) | reinterpret_cast<uintptr_t>(J) |
-                           reinterpret_cast<uintptr_t>(min_sep) | reinterpret_cast<uintptr_t>(goal_dist);
-    if (dbls % alignof(double) != 0) return fail(DPILQR_EINVAL, "policy_rollout: a device pointer is not aligned to its element type");
-    return launch_policy_rollout(*desc, X, U, K, n_samples, x0s, W, u_lim, Xs, Us, J, min_sep, goal_dist, as_stream(stream));
+    const int32_t rc = check_policy_args("policy_rollout", desc, n_samples, X, U, K, x0s, J, W, u_lim, Xs, Us, min_sep, goal_dist);
+    return rc ? rc : launch_policy_rollout(*desc, X, U, K, n_samples, x0s, W, u_lim, Xs, Us, J, min_sep, goal_dist, as_stream(stream));
 }
 
 int32_t dpilqr_policy_rollout_dec(const dpilqr_batch_desc* desc, const double* X, const double* U_ff, const double* Kc, int32_t kc_max,
                                   const uint64_t* nbr_bits, int32_t n_samples, const double* x0s, const double* W, const double* u_lim,
                                   double* Xs, double* Us, double* J, double* min_sep, double* goal_dist, void* stream) {
-    int32_t rc = check_desc(desc);
+    const int32_t rc = check_policy_args("policy_rollout_dec", desc, n_samples, X, U_ff, Kc, x0s, J, W, u_lim, Xs, Us, min_sep, goal_dist);
     if (rc) return rc;
-    if (!X || !U_ff || !Kc || !nbr_bits || !x0s || !J) return fail(DPILQR_EINVAL, "policy_rollout_dec: NULL pointer");
-    if (n_samples <= 0) return fail(DPILQR_EINVAL, "policy_rollout_dec: n_samples=%d", n_samples);
-    const uintptr_t dbls = reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(U_ff) | reinterpret_cast<uintptr_t>(Kc) |
-                           reinterpret_cast<uintptr_t>(nbr_bits) | reinterpret_cast<uintptr_t>(x0s) | reinterpret_cast<uintptr_t>(W) |
-                           reinterpret_cast<uintptr_t>(u_lim) | reinterpret_cast<uintptr_t>(Xs) | reinterpret_cast<uintptr_t>(Us) |
-                           reinterpret_cast<uintptr_t>(J) | reinterpret_cast<uintptr_t>(min_sep) | reinterpret_cast<uintptr_t>(goal_dist);
-    if (dbls % alignof(double) != 0) return fail(DPILQR_EINVAL, "policy_rollout_dec: a device pointer is not aligned to its element type");
+    if (!nbr_bits || reinterpret_cast<uintptr_t>(nbr_bits) % alignof(uint64_t) != 0)
+        return fail(DPILQR_EINVAL, "policy_rollout_dec: nbr_bits is a NULL pointer or not aligned to its element type");
     return launch_policy_rollout_dec(*desc, X, U_ff, Kc, kc_max, nbr_bits, n_samples, x0s, W, u_lim, Xs, Us, J, min_sep, goal_dist,
                                      as_stream(stream));
 }

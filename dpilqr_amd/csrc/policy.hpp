@@ -29,6 +29,13 @@
 //   stage-cost terms  per sample k reference costs and k (k - 1) / 2 pair costs, in combinations order, by parity.
 // The whole allocation is zeroed before the first step: the padding words (rs, as, ac) are never read, and no lane reads a word
 // that neither it nor a thread ordered before it by a barrier has written.
+//
+// All of the above is policy_rollout_body, written once.  What it leaves to its `Gains` argument is the K[t] image and its use:
+//   cols, mn    columns of a row of K[t] and elements of K[t] in global memory (the K buffers' parity stride is cols * rs)
+//   kStage      K[t] elements a thread stages per step, a compile-time bound: the staging arrays stay in registers
+//   setup, load   per lane, once, before the first fetch; staged element q of K[t] from global memory
+//   product     sum[c] += (K[t] dx)[a * NC + c] for lane (sl, a), from the K buffer of this parity and the sample's dx row
+// DenseGains (k_policy_rollout): the full n_u x n_x matrix.  CompactGains (policy_dec.hpp): per agent its neighbourhood's columns.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -73,17 +80,51 @@ __device__ __forceinline__ double pair_dist2(const double* a, const double* b, i
     return s;
 }
 
-// Xs [B][S][T+1][n_x], Us [B][S][T][n_u] (either may be null); J, min_sep [B][S]; goal_dist [B][S][k] (the last two may be null)
+// sum[c] += K_blk dx_o: column block `blk` of this agent's NC rows (kp: the K buffer at word a) times agent o's dx, the columns
+// in ascending order, one multiply and one add per term
 template <int NS, int NC>
-__global__ __launch_bounds__(kPolicyThreads) void k_policy_rollout(dpilqr_batch_desc D, const double* __restrict__ X,
-        const double* __restrict__ U, const double* __restrict__ K, int S, int chunks, const double* __restrict__ x0s,
-        const double* __restrict__ W, const double* __restrict__ u_lim, double* __restrict__ Xs, double* __restrict__ Us,
-        double* __restrict__ J_out, double* __restrict__ min_sep, double* __restrict__ goal_dist) {
-    constexpr int nth = kPolicyThreads;
+__device__ __forceinline__ void policy_block(double (&sum)[NC], const double* kp, const double* dxs, int blk, int o, int rs, int k, int AS) {
+    double dxv[NS], kv[NS][NC];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        dxv[i] = dxs[o * AS + i];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) kv[i][c] = kp[(blk * NS + i) * rs + c * k];
+    }
+#pragma unroll
+    for (int i = 0; i < NS; ++i)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) sum[c] += kv[i][c] * dxv[i];
+}
+
+// the dense gains K[b][t] [n_u][n_x]: every agent's rows take every agent's dx, column block o against agent o
+template <int NS, int NC>
+struct DenseGains {
+    static constexpr int kStage = kPolicyStage;
+    int k, cols, mn;
+    int ksrc[kStage];
+    __device__ explicit DenseGains(int k_) : k(k_), cols(k_ * NS), mn((k_ * NC) * (k_ * NS)) {}
+    __device__ __forceinline__ void setup(int tid, int /*b*/, int /*a*/, bool /*active*/) {
+#pragma unroll      // (no load behind a test: an element past the matrix reads its first entry)
+        for (int q = 0; q < kStage; ++q) ksrc[q] = tid + q * kPolicyThreads < mn ? tid + q * kPolicyThreads : 0;
+    }
+    __device__ __forceinline__ void load(int q, const double* Kt, int /*tid*/, double& st) const { st = Kt[ksrc[q]]; }
+    __device__ __forceinline__ void product(double (&sum)[NC], const double* kp, const double* dxs, int rs, int AS) const {
+        for (int o = 0; o < k; ++o) policy_block<NS, NC>(sum, kp, dxs, o, o, rs, k, AS);
+    }
+};
+
+// The rollout, for either form of the gains (the header comment); the pointers are the kernels' __restrict__ parameters.
+// Xs [B][S][T+1][n_x], Us [B][S][T][n_u] (either may be null); J, min_sep [B][S]; goal_dist [B][S][k] (the last two may be null)
+template <int NS, int NC, class Gains>
+__device__ __forceinline__ void policy_rollout_body(Gains G, const dpilqr_batch_desc& D, const double* X, const double* U,
+        const double* K, int S, int chunks, const double* x0s, const double* W, const double* u_lim, double* Xs, double* Us,
+        double* J_out, double* min_sep, double* goal_dist) {
+    constexpr int nth = kPolicyThreads, kStage = Gains::kStage;
     const int tid = (int)threadIdx.x;
     const int b = (int)blockIdx.x / chunks, chunk = (int)blockIdx.x - b * chunks;
-    const int k = D.k, T = D.T, n = k * NS, m = k * NC, mn = m * n;
-    const int npairs = k * (k - 1) / 2;
+    const int k = D.k, T = D.T, n = k * NS, m = k * NC;
+    const int cols = G.cols, mn = G.mn, npairs = k * (k - 1) / 2;      // columns of a row of K[t], elements of K[t]
     const PolicyLds O(NS, NC, k);
     const int AS = O.as, AC = O.ac;
     const int sl = tid / k, a = tid - sl * k;
@@ -104,29 +145,29 @@ __global__ __launch_bounds__(kPolicyThreads) void k_policy_rollout(dpilqr_batch_
     double* Uw = (Us && active) ? Us + smp * T * m + a * NC : nullptr;
 
     const int model = active ? P.model[a] : 0;
+    G.setup(tid, b, a, active);
     const double* xf = P.xf + a * NS;
     const double* Qa = P.Q + a * NS * NS;
     const double* Ra = P.R + a * NC * NC;
     const double* Qfa = P.Qf + a * NS * NS;
 
-    // the cooperative copy: element e = tid + q nth of K[t] is (row e / n, column e % n); thread tid < n holds an entry of X,
-    // thread 128 + i (i < n_u) one of U
-    int ksrc[kPolicyStage], kdst[kPolicyStage];
+    // the cooperative copy: element e = tid + q nth of K[t] is (row e / cols, column e % cols); thread tid < n holds an entry
+    // of X, thread 128 + i (i < n_u) one of U
+    int kdst[kStage];
 #pragma unroll
-    for (int q = 0; q < kPolicyStage; ++q) {
+    for (int q = 0; q < kStage; ++q) {
         const int e = tid + q * nth;
-        const int row = e / n, j = e - row * n;
-        ksrc[q] = e < mn ? e : 0;                 // (no load behind a test: an element past the matrix reads its first entry)
+        const int row = e / cols, j = e - row * cols;
         kdst[q] = e < mn ? j * O.rs + (row % NC) * k + row / NC : -1;
     }
     const bool has_x = tid < n, has_u = tid >= 128 && tid - 128 < m;
     const int xdst = has_x ? (tid / NS) * AS + tid % NS : 0;
     const int udst = has_u ? ((tid - 128) / NC) * AC + (tid - 128) % NC : 0;
-    double stK[kPolicyStage], stX = 0.0, stU = 0.0;
+    double stK[kStage], stX = 0.0, stU = 0.0;
     auto fetch = [&](int t) {     // registers <- global memory: K[t], X[t + 1], U[t + 1]
         const double* Kt = Kb + (int64_t)t * mn;
 #pragma unroll
-        for (int q = 0; q < kPolicyStage; ++q) stK[q] = Kt[ksrc[q]];
+        for (int q = 0; q < kStage; ++q) G.load(q, Kt, tid, stK[q]);
         if (t + 1 < T) {
             if (has_x) stX = Xb[(int64_t)(t + 1) * n + tid];
             if (has_u) stU = Ub[(int64_t)(t + 1) * m + (tid - 128)];
@@ -141,13 +182,11 @@ __global__ __launch_bounds__(kPolicyThreads) void k_policy_rollout(dpilqr_batch_
     double x[NS], w[NS], lo[NC], hi[NC];
     if (active) {
 #pragma unroll
-        for (int i = 0; i < NS; ++i) x[i] = x0s[smp * n + a * NS + i];
-        if (Xw) {
-#pragma unroll
-            for (int i = 0; i < NS; ++i) Xw[i] = x[i];
+        for (int i = 0; i < NS; ++i) {
+            x[i] = x0s[smp * n + a * NS + i];
+            if (Xw) Xw[i] = x[i];
+            w[i] = Wp ? Wp[i] : 0.0;
         }
-#pragma unroll
-        for (int i = 0; i < NS; ++i) w[i] = Wp ? Wp[i] : 0.0;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             lo[c] = u_lim ? u_lim[a * NC + c] : 0.0;
@@ -156,15 +195,15 @@ __global__ __launch_bounds__(kPolicyThreads) void k_policy_rollout(dpilqr_batch_
     }
     // the dimensions of this agent's pairs (min of the two agents' n_dims, cost.py:145), two bits per partner offset (k <= 20)
     unsigned long long nd_pack = 0ull;
-    if (active && !homog) {
+    if (active && !homog)
         for (int dd = 1; 2 * dd <= k; ++dd) {
             const int o = a + dd < k ? a + dd : a + dd - k;
             nd_pack |= (unsigned long long)(min(P.n_dims[a], P.n_dims[o]) & 3) << (2 * dd);
         }
-    }
     fetch(0);
     lds_handoff(false);
 
+    const bool clamp = u_lim != nullptr, noisy = W != nullptr;      // uniform: no per-lane pointer test inside the loop
     double J = 0.0, sep2 = __builtin_huge_val();
     // this agent's share of the sample's pairs at the positions in `sxs`: (a, a + 1), ..., (a, a + k / 2) mod k, each computed as
     // (lower, higher) and put where the sum in combinations order finds it (forward.hpp); the smallest squared distance is kept
@@ -178,12 +217,19 @@ __global__ __launch_bounds__(kPolicyThreads) void k_policy_rollout(dpilqr_batch_
             cp[pair_index(l, h, k)] = pair_cost(sxs + l * AS, sxs + h * AS, nd, radius);
         }
     };
+    // J += the stage cost whose terms lie in the buffers of parity p, summed in the reference's order (lane a = 0 of a sample)
+    auto add_stage_cost = [&](int p) {
+        const double* cr = lds + O.cref + (p * O.spw + sl) * k;
+        const double* cp = lds + O.cpair + (p * O.spw + sl) * O.np1;
+        const double prox = sum_in_order(cp, npairs), ref = sum_in_order(cr, k);
+        J += w_prox * prox + w_ref * ref;
+    };
 
     for (int t = 0; t < T; ++t) {
         const int par = t & 1;
-        double* sK = lds + O.Kt + par * n * O.rs;
+        double* sK = lds + O.Kt + par * cols * O.rs;
 #pragma unroll
-        for (int q = 0; q < kPolicyStage; ++q)
+        for (int q = 0; q < kStage; ++q)
             if (kdst[q] >= 0) sK[kdst[q]] = stK[q];
         if (t + 1 < T) {
             if (has_x) lds[O.Xt + (par ^ 1) * k * AS + xdst] = stX;
@@ -203,7 +249,7 @@ __global__ __launch_bounds__(kPolicyThreads) void k_policy_rollout(dpilqr_batch_
                 sxs[tid * AS + i] = x[i];
                 wt[i] = w[i];
             }
-            if (Wp && t + 1 < T) {
+            if (noisy && t + 1 < T) {
 #pragma unroll
                 for (int i = 0; i < NS; ++i) w[i] = Wp[(int64_t)(t + 1) * n + i];
             }
@@ -211,35 +257,15 @@ __global__ __launch_bounds__(kPolicyThreads) void k_policy_rollout(dpilqr_batch_
         if (t + 1 < T) fetch(t + 1);
         lds_handoff(false);
         if (active) {
-            // K[t] dx, this agent's NC rows, the columns in ascending order, one multiply and one add per term
-            double sum[NC];
+            double sum[NC];      // K[t] dx, this agent's NC rows
 #pragma unroll
             for (int c = 0; c < NC; ++c) sum[c] = 0.0;
-            const double* kp = sK + a;
-            const double* dxs = sdx + sl * k * AS;
-            for (int o = 0; o < k; ++o) {
-                double dxv[NS], kv[NS][NC];
-#pragma unroll
-                for (int i = 0; i < NS; ++i) {
-                    dxv[i] = dxs[o * AS + i];
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) kv[i][c] = kp[(o * NS + i) * O.rs + c * k];
-                }
-#pragma unroll
-                for (int i = 0; i < NS; ++i)
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) sum[c] += kv[i][c] * dxv[i];
-            }
-            if (a == 0 && t > 0) {  // stage cost of step t - 1 (other parity), summed in the reference's order
-                const double* cr = lds + O.cref + ((par ^ 1) * O.spw + sl) * k;
-                const double* cp = lds + O.cpair + ((par ^ 1) * O.spw + sl) * O.np1;
-                const double prox = sum_in_order(cp, npairs), ref = sum_in_order(cr, k);
-                J += w_prox * prox + w_ref * ref;
-            }
+            G.product(sum, sK + a, sdx + sl * k * AS, O.rs, AS);
+            if (a == 0 && t > 0) add_stage_cost(par ^ 1);      // of step t - 1
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
                 double v = ut[c] + sum[c];
-                if (u_lim) v = v < lo[c] ? lo[c] : (v > hi[c] ? hi[c] : v);     // a NaN stays a NaN
+                if (clamp) v = v < lo[c] ? lo[c] : (v > hi[c] ? hi[c] : v);     // a NaN stays a NaN
                 ut[c] = v;
             }
             lds[O.cref + (par * O.spw + sl) * k + a] = ref_cost<NS, NC>(x, ut, xf, Qa, Ra, false);
@@ -251,61 +277,51 @@ __global__ __launch_bounds__(kPolicyThreads) void k_policy_rollout(dpilqr_batch_
             double xn[NS];
             integrate_rt<NS>(model, x, ut, dtr, xn);
 #pragma unroll
-            for (int i = 0; i < NS; ++i) x[i] = Wp ? xn[i] + wt[i] : xn[i];
+            for (int i = 0; i < NS; ++i) x[i] = noisy ? xn[i] + wt[i] : xn[i];
             if (Xw) {
 #pragma unroll
                 for (int i = 0; i < NS; ++i) Xw[(int64_t)(t + 1) * n + i] = x[i];
             }
         }
     }
-    {
-        // last stage cost, then the terminal cost cost(x_T, 0, terminal=True) (control.py:91); x_T counts for min_sep too
-        const int par = T & 1;
-        double* sxs = lds + O.xs + par * O.spw * k * AS;
-        if (active) {
+    // last stage cost, then the terminal cost cost(x_T, 0, terminal=True) (control.py:91); x_T counts for min_sep too
+    const int par = T & 1;
+    double* sxs = lds + O.xs + par * O.spw * k * AS;
+    if (active) {
 #pragma unroll
-            for (int i = 0; i < NS; ++i) sxs[tid * AS + i] = x[i];
-        }
-        lds_handoff(false);
-        if (active) {
-            if (a == 0) {
-                const double* cr = lds + O.cref + ((par ^ 1) * O.spw + sl) * k;
-                const double* cp = lds + O.cpair + ((par ^ 1) * O.spw + sl) * O.np1;
-                const double prox = sum_in_order(cp, npairs), ref = sum_in_order(cr, k);
-                J += w_prox * prox + w_ref * ref;
-            }
-            double uz[NC];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) uz[c] = 0.0;
-            lds[O.cref + (par * O.spw + sl) * k + a] = ref_cost<NS, NC>(x, uz, xf, Qfa, Ra, true);
-            pairs(sxs + sl * k * AS, lds + O.cpair + (par * O.spw + sl) * O.np1);
-            lds[O.sep + tid] = sep2;
-        }
-        lds_handoff(false);
-        if (active) {
-            if (a == 0) {
-                const double* cr = lds + O.cref + (par * O.spw + sl) * k;
-                const double* cp = lds + O.cpair + (par * O.spw + sl) * O.np1;
-                const double prox = sum_in_order(cp, npairs), ref = sum_in_order(cr, k);
-                J += w_prox * prox + w_ref * ref;
-                J_out[smp] = J;
-                if (min_sep) {
-                    double mn2 = __builtin_huge_val();      // no pair (k = 1): +inf
-                    for (int i = 0; i < k; ++i) mn2 = fmin(mn2, lds[O.sep + sl * k + i]);
-                    min_sep[smp] = sqrt(mn2);
-                }
-            }
-            if (goal_dist) {
-                const int nd = P.n_dims[a];
-                double g2 = 0.0;
-                for (int c = 0; c < nd && c < NS; ++c) {
-                    const double df = x[c] - xf[c];
-                    g2 += df * df;
-                }
-                goal_dist[smp * k + a] = sqrt(g2);
-            }
-        }
+        for (int i = 0; i < NS; ++i) sxs[tid * AS + i] = x[i];
     }
+    lds_handoff(false);
+    if (active) {
+        if (a == 0) add_stage_cost(par ^ 1);
+        double uz[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) uz[c] = 0.0;
+        lds[O.cref + (par * O.spw + sl) * k + a] = ref_cost<NS, NC>(x, uz, xf, Qfa, Ra, true);
+        pairs(sxs + sl * k * AS, lds + O.cpair + (par * O.spw + sl) * O.np1);
+        lds[O.sep + tid] = sep2;
+    }
+    lds_handoff(false);
+    if (active) {
+        if (a == 0) {
+            add_stage_cost(par);
+            J_out[smp] = J;
+            if (min_sep) {
+                double mn2 = __builtin_huge_val();      // no pair (k = 1): +inf
+                for (int i = 0; i < k; ++i) mn2 = fmin(mn2, lds[O.sep + sl * k + i]);
+                min_sep[smp] = sqrt(mn2);
+            }
+        }
+        if (goal_dist) goal_dist[smp * k + a] = sqrt(pair_dist2(x, xf, min(P.n_dims[a], NS)));
+    }
+}
+
+template <int NS, int NC>
+__global__ __launch_bounds__(kPolicyThreads) void k_policy_rollout(dpilqr_batch_desc D, const double* __restrict__ X,
+        const double* __restrict__ U, const double* __restrict__ K, int S, int chunks, const double* __restrict__ x0s,
+        const double* __restrict__ W, const double* __restrict__ u_lim, double* __restrict__ Xs, double* __restrict__ Us,
+        double* __restrict__ J_out, double* __restrict__ min_sep, double* __restrict__ goal_dist) {
+    policy_rollout_body<NS, NC>(DenseGains<NS, NC>(D.k), D, X, U, K, S, chunks, x0s, W, u_lim, Xs, Us, J_out, min_sep, goal_dist);
 }
 
 }  // namespace dpilqr

@@ -3,7 +3,7 @@
 figures (share of samples without a bound, largest sensitivity among the bounded ones, clamped share of the u_lim run, share of
 samples inside the radius, share of samples whose cost the perturbed start moves by 1 % and more) and, on a GPU, the worst
 measured error / bound ratio of every variant; then, on a GPU, per case of tests/policy_cases.py whether the sparse kernel fed
-full masks returns the dense kernel's results bit for bit (recorded, not asserted anywhere).
+full masks returns the dense kernel's results bit for bit (recorded here; tests/test_gpu_policy_dec.py asserts it).
 
     python scripts/policy_dec_sensitivity.py [--no-gpu] [--out profiles/policy_dec_sensitivity.txt]"""
 import argparse

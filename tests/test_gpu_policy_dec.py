@@ -8,9 +8,9 @@ kc_max: item 0 of every case has full masks, so the true maximum of the three-it
 run; the items 1 and 2 alone (every agent alone; random masks, all smaller than k) run once with their true maximum and once with
 kc_max = k: finite, equal to one another and to the same items of the three-item run.
 
-With all masks full the results are held to ProblemBatch.policy_rollout on the same dense K within the per-sample bound of
-tests/policy_cases.py (whether they are bit-identical is printed here and recorded by scripts/policy_dec_sensitivity.py in
-profiles/policy_dec_sensitivity.txt, not asserted)."""
+With all masks full the results are held to ProblemBatch.policy_rollout on the same dense K: bit for bit -- the two kernels are
+one rollout body (csrc/policy.hpp) with two descriptions of the gains, and with full masks both descriptions add the same
+products in the same order -- and, as before, within the per-sample bound of tests/policy_cases.py."""
 import numpy as np
 import pytest
 
@@ -130,8 +130,9 @@ def test_full_masks_agree_with_the_dense_kernel(case):
         W, lim = ref.args(v)
         dense = _host(pb.policy_rollout(ref.X, ref.U, ref.K, b["x0s"], W=W, u_lim=lim, trajectories=True))
         dec = _host(pb.policy_rollout_dec(ref.X, ref.U, Kc, masks, b["x0s"], W=W, u_lim=lim, trajectories=True))
-        same = all(np.array_equal(dense[key], dec[key]) for key in dense)
-        print(f"{case.id} {v}: full-mask sparse rollout bit-identical to the dense one: {same}")
+        assert set(dec) == set(dense) == {"X", "U", "J", "min_sep", "goal_dist"}
+        for key in dense:
+            assert np.array_equal(dense[key], dec[key]), (v, key)
         unchecked = 0
         for i in range(B):
             for s in range(case.S):
