@@ -96,6 +96,7 @@ SIGNATURES = {
 # additive entry points of the extension headers dpilqr_hip.h includes (include/dpilqr_policy.h); bound by load() like the rest
 EXT_SIGNATURES = {
     "dpilqr_policy_rollout": (i32, [_DP, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "dpilqr_policy_rollout_large": (i32, [_DP, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dpilqr_policy_rollout_dec": (i32, [_DP, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dpilqr_dispatch_stitch_policy": (i32, [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
 }

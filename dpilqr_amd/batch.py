@@ -8,7 +8,7 @@ Python objects on the hot path:
     ilqrSolver._backward_pass  control.py:116-148  -> ProblemBatch.make_tiles + backward_pass_tiles
     ilqrSolver._forward_pass   control.py:95-114   -> ProblemBatch.forward_pass
     ilqrSolver.solve           control.py:150-225  -> ProblemBatch.solve
-    (no reference counterpart: the feedback policy closed loop)  -> ProblemBatch.policy_rollout, .policy_rollout_dec
+    (no reference counterpart: the feedback policy closed loop)  -> ProblemBatch.policy_rollout, .policy_rollout_large, .policy_rollout_dec
 """
 import ctypes as C
 import os
@@ -207,6 +207,11 @@ class ProblemBatch:
         no tile records exist (one would be 1.28 MB at n_x = 240)."""
         return self.n_x > 60
 
+    @property
+    def is_large(self):
+        """n_x > 60: the large-cluster kernels serve this batch (the fused sweep above, policy_rollout_large below)."""
+        return self.n_x > 60
+
     def _in(self, a, shape, dtype=torch.float64):
         t = to_dev(a, dtype)
         if tuple(t.shape) != tuple(shape):
@@ -329,6 +334,28 @@ class ProblemBatch:
         _lib.check(self._lib.dpilqr_policy_rollout(self._d, ptr(X), ptr(U), ptr(K), S, ptr(x0s), ptr(W), ptr(u_lim),
                                                    ptr(out.get("X")), ptr(out.get("U")), ptr(out["J"]), ptr(out["min_sep"]),
                                                    ptr(out["goal_dist"]), stream_handle()))
+        return out
+
+    def _policy_large_shapes(self, X, U, K, x0s, W, u_lim):
+        """Host-side validation of policy_rollout_large's arguments (no device access): returns the number of samples per item."""
+        B, T, k, n, m = self.B, self.T, self.k, self.n_x, self.n_u
+        if n <= 60:
+            raise ValueError(f"policy_rollout_large serves clusters of 60 < n_x <= 240, this batch has n_x = {n}: use policy_rollout")
+        if n > 240 or k > 20 or (self.n_s, self.n_c) not in ((4, 2), (6, 3), (12, 4)):
+            raise ValueError(f"policy_rollout_large serves clusters of 60 < n_x <= 240 and k <= 20 of the four-, six- and twelve-state "
+                             f"families, this batch has n_x = {n}, k = {k}, (n_s, n_c) = ({self.n_s}, {self.n_c})")
+        return self._policy_common("policy_rollout_large", X, x0s, W, u_lim, (("U", U, (B, T, m)), ("K", K, (B, T, m, n))))
+
+    def policy_rollout_large(self, X, U, K, x0s, W=None, u_lim=None, trajectories=False):
+        """policy_rollout for large clusters, 60 < n_x <= 240 with k <= 20 (dpilqr_policy_rollout_large): the same arguments and
+        the same returned dict.  K[t] (x_t - X[t]) is formed on the fp64 matrix pipe -- the columns in ascending order, one fused
+        multiply-add per term -- so a control may differ from policy_rollout's arithmetic in the last bits."""
+        S = self._policy_large_shapes(X, U, K, x0s, W, u_lim)
+        X, U, x0s, W, u_lim, out = self._policy_stage(S, X, U, x0s, W, u_lim, trajectories)
+        K = self._in(K, (self.B, self.T, self.n_u, self.n_x))
+        _lib.check(self._lib.dpilqr_policy_rollout_large(self._d, ptr(X), ptr(U), ptr(K), S, ptr(x0s), ptr(W), ptr(u_lim),
+                                                         ptr(out.get("X")), ptr(out.get("U")), ptr(out["J"]), ptr(out["min_sep"]),
+                                                         ptr(out["goal_dist"]), stream_handle()))
         return out
 
     def _policy_dec_shapes(self, X, U_ff, Kc, nbr_bits, x0s, W, u_lim, check_masks=True):

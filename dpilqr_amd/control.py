@@ -110,8 +110,9 @@ class ilqrSolver:
     # ---- the policy, closed loop
     def closed_loop(self, X, U, x0s, W=None, u_lim=None, mu=0.0, trajectories=False):
         """Run the feedback policy u_t = U[t] + K[t] (x_t - X[t]) of the trajectory (X, U) from every start in x0s (S, n_x),
-        on the device in one launch (ProblemBatch.policy_rollout): W (S, N, n_x) is an additive disturbance on x_{t+1}, u_lim
-        (2, n_u) lower / upper control limits.  Returns host arrays J (S,), min_sep (S,), goal_dist (S, n_agents) and, with
+        on the device in one launch (ProblemBatch.policy_rollout; problems of more than 60 states: policy_rollout_large, which
+        forms K[t] (x_t - X[t]) on the matrix pipe, for up to 240 states and 20 agents): W (S, N, n_x) is an additive disturbance
+        on x_{t+1}, u_lim (2, n_u) lower / upper control limits.  Returns host arrays J (S,), min_sep (S,), goal_dist (S, n_agents) and, with
         trajectories=True, X (S, N+1, n_x), U (S, N, n_u).
 
         The gains come from ONE backward pass at the given (X, U) with regularisation mu, so that they belong to that
@@ -130,8 +131,9 @@ class ilqrSolver:
             raise ValueError(f"closed_loop: x0s has shape {x0s.shape}, expected (n_samples, {self.n_x})")
         pb = self._pb(self.N)
         K, _ = pb.backward_pass(X[None], U[None], float(mu))
-        r = pb.policy_rollout(X[None], U[None], K, x0s[None], W=None if W is None else np.asarray(W, dtype=np.float64)[None],
-                              u_lim=u_lim, trajectories=trajectories)
+        rollout = pb.policy_rollout_large if pb.is_large else pb.policy_rollout      # (backward_pass routes on the same size)
+        r = rollout(X[None], U[None], K, x0s[None], W=None if W is None else np.asarray(W, dtype=np.float64)[None],
+                    u_lim=u_lim, trajectories=trajectories)
         return {key: v[0].cpu().numpy() for key, v in r.items()}
 
     # ---- the solve

@@ -770,7 +770,7 @@ int32_t dpilqr_forward_pass(const dpilqr_batch_desc* desc, const double* X, cons
                           n_alpha, Xn, Un, Jn, S, nullptr, nullptr, desc->B, as_stream(stream));
 }
 
-// the argument checks the two closed-loop rollouts share, under the caller's name (W ... goal_dist may be null)
+// the argument checks the closed-loop rollouts share, under the caller's name (W ... goal_dist may be null)
 static int32_t check_policy_args(const char* who, const dpilqr_batch_desc* desc, int32_t n_samples, const double* X, const double* U,
                                  const double* K, const double* x0s, const double* J, const double* W, const double* u_lim,
                                  const double* Xs, const double* Us, const double* min_sep, const double* goal_dist) {
@@ -789,6 +789,13 @@ int32_t dpilqr_policy_rollout(const dpilqr_batch_desc* desc, const double* X, co
                               double* min_sep, double* goal_dist, void* stream) {
     const int32_t rc = check_policy_args("policy_rollout", desc, n_samples, X, U, K, x0s, J, W, u_lim, Xs, Us, min_sep, goal_dist);
     return rc ? rc : launch_policy_rollout(*desc, X, U, K, n_samples, x0s, W, u_lim, Xs, Us, J, min_sep, goal_dist, as_stream(stream));
+}
+
+int32_t dpilqr_policy_rollout_large(const dpilqr_batch_desc* desc, const double* X, const double* U, const double* K, int32_t n_samples,
+                                    const double* x0s, const double* W, const double* u_lim, double* Xs, double* Us, double* J,
+                                    double* min_sep, double* goal_dist, void* stream) {
+    const int32_t rc = check_policy_args("policy_rollout_large", desc, n_samples, X, U, K, x0s, J, W, u_lim, Xs, Us, min_sep, goal_dist);
+    return rc ? rc : launch_policy_rollout_large(*desc, X, U, K, n_samples, x0s, W, u_lim, Xs, Us, J, min_sep, goal_dist, as_stream(stream));
 }
 
 int32_t dpilqr_policy_rollout_dec(const dpilqr_batch_desc* desc, const double* X, const double* U_ff, const double* Kc, int32_t kc_max,

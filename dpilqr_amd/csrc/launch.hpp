@@ -5,8 +5,8 @@
 // batched entry points), tu_big.hip (the sweep for n_x > 60 and the fp32 arm), tu_bigfwd.hip (their forward passes),
 // tu_team.hip (the fused wavefront sweeps with a helper wavefront per item), tu_inprod.hip (the wavefront sweeps with in-sweep
 // production), tu_bike.hip (the same for the five-state family, BikeDynamics5D), tu_lsteam.hip (the line search with two
-// wavefronts per item), tu_frontend.hip (the device-side dispatch front / back end), tu_policy.hip (the closed-loop ensemble rollouts) and
-// dpilqr_hip.hip (the C ABI and the solve loop).
+// wavefronts per item), tu_frontend.hip (the device-side dispatch front / back end), tu_policy.hip (the closed-loop ensemble rollouts),
+// tu_policy_large.hip (the same for n_x > 60) and dpilqr_hip.hip (the C ABI and the solve loop).
 // No device code crosses a file boundary.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -218,6 +218,11 @@ int32_t launch_policy_rollout(const dpilqr_batch_desc& D, const double* X, const
 int32_t launch_policy_rollout_dec(const dpilqr_batch_desc& D, const double* X, const double* U_ff, const double* Kc, int32_t kc_max,
                                   const uint64_t* nbr_bits, int32_t n_samples, const double* x0s, const double* W, const double* u_lim,
                                   double* Xs, double* Us, double* J, double* min_sep, double* goal_dist, hipStream_t st);
+
+// ---- tu_policy_large.hip: the same rollout for 60 < n_x <= 240, K[t] dx on the matrix pipe (policy_large.hpp); enqueue only
+int32_t launch_policy_rollout_large(const dpilqr_batch_desc& D, const double* X, const double* U, const double* K, int32_t n_samples,
+                                    const double* x0s, const double* W, const double* u_lim, double* Xs, double* Us, double* J,
+                                    double* min_sep, double* goal_dist, hipStream_t st);
 
 // ---- tu_big.hip: large clusters (n_x > 60) in fp64, any size in fp32 (BASELINE config 5's tolerance study)
 int64_t riccati_big_scratch_elems(int n, int m);   // per sub-problem in flight, in elements of the arithmetic type

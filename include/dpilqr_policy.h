@@ -36,6 +36,20 @@ int32_t dpilqr_policy_rollout(const dpilqr_batch_desc* desc, const double* X, co
                               int32_t n_samples, const double* x0s, const double* W, const double* u_lim, double* Xs,
                               double* Us, double* J, double* min_sep, double* goal_dist, void* stream);
 
+/* The same rollout for LARGE clusters, 60 < n_x <= 240 with k <= 20: the four-, six- and twelve-state families, models mixed
+ * within a family (the padded HumanDynamics6D among twelve-state agents included) -- BASELINE config 5's twenty heterogeneous
+ * agents, n_x = 240, n_u = 80, are the largest.  Arguments, shapes and results are dpilqr_policy_rollout's, with ONE difference
+ * in the arithmetic: K[b][t] (x_t - X[b][t]) of all the samples a workgroup holds is one (n_u x n_x)(n_x x samples) product on
+ * the fp64 matrix pipe, so each u_t entry is U[b][t] + (the sum over columns 0 .. n_x-1 in that order, ONE FUSED multiply-add
+ * per term, starting from zero) -- where dpilqr_policy_rollout rounds every product and every addition separately.  K[t] is
+ * read from global memory once per workgroup and step and never staged (csrc/policy_large.hpp).
+ * DPILQR_EINVAL: the NULL, alignment and n_samples conditions of dpilqr_policy_rollout.  DPILQR_EUNSUPPORTED, before any launch:
+ * n_x <= 60 (that is dpilqr_policy_rollout's range), n_x > 240, k > 20, more than 2^31 - 1 workgroups.  B = 0: DPILQR_OK, nothing
+ * is launched.  fp64 only.  Enqueue only, nothing is allocated. */
+int32_t dpilqr_policy_rollout_large(const dpilqr_batch_desc* desc, const double* X, const double* U, const double* K,
+                                    int32_t n_samples, const double* x0s, const double* W, const double* u_lim, double* Xs,
+                                    double* Us, double* J, double* min_sep, double* goal_dist, void* stream);
+
 /* The closed loop of a DISTRIBUTED solution (dpilqr_dispatch_* of dpilqr_hip.h): every agent runs the feedback law of the
  * sub-problem solved for its own neighbourhood.  Agent i of item b has the neighbourhood mask nbr_bits[b][i] (bit j = agent j;
  * bit i set; the masks need not be symmetric), C_i its members in ascending order, kc_i their number, kw = kc_max * n_s.
