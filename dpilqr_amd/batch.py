@@ -9,6 +9,7 @@ Python objects on the hot path:
     ilqrSolver._forward_pass   control.py:95-114   -> ProblemBatch.forward_pass
     ilqrSolver.solve           control.py:150-225  -> ProblemBatch.solve
     (no reference counterpart: the feedback policy closed loop)  -> ProblemBatch.policy_rollout, .policy_rollout_large, .policy_rollout_dec
+    (the step between two solves of a receding-horizon loop on a real plant)  -> ProblemBatch.policy_advance, .policy_advance_dec
 """
 import ctypes as C
 import os
@@ -372,21 +373,26 @@ class ProblemBatch:
         S = self._policy_common("policy_rollout_dec", X, x0s, W, u_lim, (("U_ff", U_ff, (B, T, m)), ("nbr_bits", nbr_bits, (B, k))))
         if not check_masks:
             return S, kc_max, None
-        # the masks: DPILQR_EINVAL of include/dpilqr_policy.h, decided here because the C entry point only enqueues
+        return S, kc_max, self._checked_masks("policy_rollout_dec", nbr_bits, kc_max)
+
+    def _checked_masks(self, who, nbr_bits, kc_max):
+        """The masks' contract -- DPILQR_EINVAL of include/dpilqr_policy.h, decided here because the C entry points only
+        enqueue --: returns them as a host int64 array.  Reads them back when they are a device tensor (B * k words)."""
+        B, k = self.B, self.k
         bits = nbr_bits.cpu().numpy() if isinstance(nbr_bits, torch.Tensor) else np.asarray(nbr_bits)
         if bits.dtype.kind not in "iu":
-            raise ValueError(f"policy_rollout_dec: nbr_bits has dtype {bits.dtype}, expected integer bit masks")
+            raise ValueError(f"{who}: nbr_bits has dtype {bits.dtype}, expected integer bit masks")
         bits = np.ascontiguousarray(bits.astype(np.uint64) & np.uint64((1 << k) - 1))
         own = np.uint64(1) << np.arange(k, dtype=np.uint64)
         if not bool(((bits & own[None, :]) != 0).all()):
-            raise ValueError("policy_rollout_dec: a neighbourhood mask lacks its agent's own bit (DPILQR_EINVAL)")
+            raise ValueError(f"{who}: a neighbourhood mask lacks its agent's own bit (DPILQR_EINVAL)")
         count = np.zeros((B, k), dtype=np.int64)
         for j in range(k):
             count += ((bits >> np.uint64(j)) & np.uint64(1)).astype(np.int64)
         if int(count.max(initial=0)) > kc_max:
-            raise ValueError(f"policy_rollout_dec: a neighbourhood mask has {int(count.max())} members, Kc holds kc_max = {kc_max} "
+            raise ValueError(f"{who}: a neighbourhood mask has {int(count.max())} members, Kc holds kc_max = {kc_max} "
                              "(DPILQR_EINVAL)")
-        return S, kc_max, bits.view(np.int64)
+        return bits.view(np.int64)
 
     def policy_rollout_dec(self, X, U_ff, Kc, nbr_bits, x0s, W=None, u_lim=None, trajectories=False, masks_checked=None):
         """The closed loop of a distributed solution (dpilqr_policy_rollout_dec): agent i of item b applies
@@ -405,6 +411,127 @@ class ProblemBatch:
                                                        ptr(u_lim), ptr(out.get("X")), ptr(out.get("U")), ptr(out["J"]),
                                                        ptr(out["min_sep"]), ptr(out["goal_dist"]), stream_handle()))
         return out
+
+    # ------------------------------------------------------------------ the receding-horizon advance
+    ADVANCE_STATE = ("x_cur", "n_done", "X_exec", "U_exec", "J_exec", "min_sep", "dist_left", "U_next", "X_next")
+
+    def advance_state(self, x0, L):
+        """The state of a receding-horizon loop over S scenarios of this batch's shape with room for L executed steps, as
+        policy_advance keeps it: a dict of device tensors x_cur (S,n_x) = x0, n_done (S,) int32 = 0, X_exec (S,L+1,n_x),
+        U_exec (S,L,n_u), J_exec (S,) = 0, min_sep (S,) = +inf, dist_left (S,k) (NaN until a scenario's first advance),
+        U_next (S,T,n_u), X_next (S,T+1,n_x)."""
+        x0 = to_dev(x0).reshape(-1, self.n_x).contiguous().clone()
+        S, L = int(x0.shape[0]), int(L)
+        if L < 1:
+            raise ValueError(f"advance_state: L = {L}, the capacity is at least one step")
+        return dict(x_cur=x0, n_done=zeros((S,), torch.int32), X_exec=zeros((S, L + 1, self.n_x)), U_exec=zeros((S, L, self.n_u)),
+                    J_exec=zeros((S,)), min_sep=torch.full((S,), float("inf"), dtype=torch.float64, device=x0.device),
+                    dist_left=torch.full((S, self.k), float("nan"), dtype=torch.float64, device=x0.device),
+                    U_next=zeros((S, self.T, self.n_u)), X_next=zeros((S, self.T + 1, self.n_x)))
+
+    def _advance_shapes(self, who, X, h, state, scen, W, u_lim, n_d, others):
+        """Host-side validation of what policy_advance and policy_advance_dec share (no device access): returns (S, L)."""
+        B, T, k, n, m = self.B, self.T, self.k, self.n_x, self.n_u
+        if n > 60 or k > 20:
+            raise ValueError(f"{who} serves clusters up to n_x = 60 and k = 20, this batch has n_x = {n}, k = {k}")
+        shape = lambda a: tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)
+        for name, a, want in (("X", X, (B, T + 1, n)),) + tuple(others):
+            if a is not None and shape(a) != want:
+                raise ValueError(f"{who}: {name} has shape {shape(a)}, expected {want}")
+        if int(h) != h or not 1 <= h <= T:
+            raise ValueError(f"{who}: h = {h}, a round executes 1 .. T = {T} steps")
+        if int(n_d) != n_d or not 1 <= n_d <= self.n_s:
+            raise ValueError(f"{who}: n_d = {n_d}, an agent has n_s = {self.n_s} states")
+        get = (lambda f: state.get(f)) if isinstance(state, dict) else (lambda f: getattr(state, f, None))
+        missing = [f for f in self.ADVANCE_STATE if not isinstance(get(f), torch.Tensor)]
+        if missing:
+            raise ValueError(f"{who}: state lacks the device tensors {missing} (ProblemBatch.advance_state makes one)")
+        sx, su = shape(get("x_cur")), shape(get("U_exec"))
+        if len(sx) != 2 or sx[1] != n or len(su) != 3 or su[1] < 1:
+            raise ValueError(f"{who}: state x_cur {sx}, U_exec {su}: expected (S, {n}) and (S, L >= 1, {m})")
+        S, L = int(sx[0]), int(su[1])
+        want = dict(x_cur=(S, n), n_done=(S,), X_exec=(S, L + 1, n), U_exec=(S, L, m), J_exec=(S,), min_sep=(S,), dist_left=(S, k),
+                    U_next=(S, T, m), X_next=(S, T + 1, n))
+        for f, w in want.items():
+            t = get(f)
+            if shape(t) != w or t.dtype != (torch.int32 if f == "n_done" else torch.float64) or not t.is_contiguous():
+                raise ValueError(f"{who}: state {f} is {shape(t)} {t.dtype}, expected contiguous {w} "
+                                 f"{'int32' if f == 'n_done' else 'float64'}")
+        if scen is None:
+            if S < B:
+                raise ValueError(f"{who}: the state holds {S} scenarios for {B} items and no scen names theirs")
+        else:
+            if shape(scen) != (B,):
+                raise ValueError(f"{who}: scen has shape {shape(scen)}, expected {(B,)}")
+            if not isinstance(scen, torch.Tensor):
+                sc = np.asarray(scen)
+                if sc.dtype.kind not in "iu" or (sc.size and (sc.min() < 0 or sc.max() >= S)) or np.unique(sc).size != sc.size:
+                    raise ValueError(f"{who}: scen must name {B} distinct scenarios out of 0 .. {S - 1}")
+            elif scen.dtype not in (torch.int32, torch.int64):
+                raise ValueError(f"{who}: scen has dtype {scen.dtype}, expected integers")
+        if W is not None and shape(W) != (S, L, n):
+            raise ValueError(f"{who}: W has shape {shape(W)}, expected {(S, L, n)} (scenarios, capacity, n_x)")
+        if u_lim is not None:
+            if shape(u_lim) != (2, m):
+                raise ValueError(f"{who}: u_lim has shape {shape(u_lim)}, expected {(2, m)} (lower row, upper row)")
+            lim = u_lim.cpu().numpy() if isinstance(u_lim, torch.Tensor) else np.asarray(u_lim, dtype=np.float64)
+            if not bool((lim[0] <= lim[1]).all()):
+                raise ValueError(f"{who}: u_lim has a lower limit above its upper limit")
+        return S, L
+
+    def _advance_args(self, X, U, state, scen, W, u_lim, S, L):
+        B, T, n, m = self.B, self.T, self.n_x, self.n_u
+        X = self._in(X, (B, T + 1, n)); U = self._in(U, (B, T, m))
+        scen = None if scen is None else to_dev(scen, torch.int32)
+        W = None if W is None else self._in(W, (S, L, n))
+        u_lim = None if u_lim is None else self._in(u_lim, (2, m))
+        st = [state[f] if isinstance(state, dict) else getattr(state, f) for f in self.ADVANCE_STATE]
+        for name, t in (("U_next", st[7]), ("X_next", st[8])):
+            if t.data_ptr() in (X.data_ptr(), U.data_ptr()):
+                raise ValueError(f"policy_advance: state {name} aliases the plan it is the shift of")
+        return X, U, scen, W, u_lim, [ptr(t) for t in st]
+
+    def policy_advance(self, X, U, K, h, state, scen=None, W=None, u_lim=None, n_d=2):
+        """The step between two solves of a receding-horizon loop (dpilqr_policy_advance): every item j -- a running scenario,
+        s = scen[j] of the S the state holds (scen None: s = j) -- executes h steps of its own plan X (B,T+1,n_x), U (B,T,n_u)
+        under the gains K (B,T,n_u,n_x) (None: open loop) from state['x_cur'][s], W (S,L,n_x) read at the scenario's own step
+        count, u_lim (2,n_u) as policy_rollout.  `state` (advance_state) is updated in place: the executed states, controls
+        and cost are appended at n_done[s] (never past the capacity L), min_sep and dist_left (over n_d coordinates) follow the
+        plant, and U_next / X_next receive the plan shifted by the executed steps, the plant's state in front: the next
+        round's warm start.  Scenarios not named are not touched.  Returns state."""
+        B, T, n, m = self.B, self.T, self.n_x, self.n_u
+        S, L = self._advance_shapes("policy_advance", X, h, state, scen, W, u_lim, n_d, (("U", U, (B, T, m)), ("K", K, (B, T, m, n))))
+        X, U, scen, W, u_lim, st = self._advance_args(X, U, state, scen, W, u_lim, S, L)
+        K = None if K is None else self._in(K, (B, T, m, n))
+        _lib.check(self._lib.dpilqr_policy_advance(self._d, ptr(X), ptr(U), ptr(K), int(h), ptr(scen), S, L, int(n_d), ptr(W),
+                                                   ptr(u_lim), *st, stream_handle()))
+        return state
+
+    def policy_advance_dec(self, X, U_ff, Kc, nbr_bits, h, state, scen=None, W=None, u_lim=None, n_d=2, masks_checked=None):
+        """policy_advance under a distributed solution's policy (dpilqr_policy_advance_dec): X the stitched trajectory, U_ff,
+        Kc (B,T,k,n_c,kc_max*n_s) and nbr_bits (B,k) as policy_rollout_dec takes them, masks_checked included.  Kc None: the
+        plan U_ff (then U_dec) is executed open loop and the masks are not read."""
+        B, T, k, n, m, ns, nc = self.B, self.T, self.k, self.n_x, self.n_u, self.n_s, self.n_c
+        who = "policy_advance_dec"
+        kc_max = 1
+        if Kc is not None:
+            sk = tuple(Kc.shape) if isinstance(Kc, torch.Tensor) else np.shape(Kc)
+            if len(sk) != 5 or sk[:4] != (B, T, k, nc) or sk[4] < ns or sk[4] % ns or sk[4] > n:
+                raise ValueError(f"{who}: Kc has shape {sk}, expected ({B}, {T}, {k}, {nc}, kc_max * {ns}) with 1 <= kc_max <= {k}")
+            kc_max = sk[4] // ns
+        others = (("U_ff", U_ff, (B, T, m)),) + ((("nbr_bits", nbr_bits, (B, k)),) if Kc is not None else ())
+        S, L = self._advance_shapes(who, X, h, state, scen, W, u_lim, n_d, others)
+        bits = None
+        if Kc is not None:
+            if nbr_bits is None:
+                raise ValueError(f"{who}: gains without neighbourhood masks")
+            trusted = masks_checked is not None and masks_checked is nbr_bits and isinstance(nbr_bits, torch.Tensor) and nbr_bits.dtype == torch.int64
+            bits = nbr_bits.contiguous() if trusted else torch.from_numpy(self._checked_masks(who, nbr_bits, kc_max)).to(device())
+            Kc = self._in(Kc, (B, T, k, nc, kc_max * ns))
+        X, U_ff, scen, W, u_lim, st = self._advance_args(X, U_ff, state, scen, W, u_lim, S, L)
+        _lib.check(self._lib.dpilqr_policy_advance_dec(self._d, ptr(X), ptr(U_ff), ptr(Kc), kc_max, ptr(bits), int(h), ptr(scen), S, L,
+                                                       int(n_d), ptr(W), ptr(u_lim), *st, stream_handle()))
+        return state
 
     def cost(self, x, u, terminal=False):
         """GameCost.__call__ at n_pts points per item: x (B,n_pts,n_x), u (B,n_pts,n_u) -> (B,n_pts)."""

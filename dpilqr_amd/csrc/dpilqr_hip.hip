@@ -809,6 +809,53 @@ int32_t dpilqr_policy_rollout_dec(const dpilqr_batch_desc* desc, const double* X
                                      as_stream(stream));
 }
 
+// the argument checks of the two receding-horizon advances (K, W, u_lim, scen may be null)
+static int32_t check_advance_args(const char* who, const dpilqr_batch_desc* desc, const double* X, const double* U, const double* K,
+                                  int32_t h, const int32_t* scen, int32_t n_scen, int32_t L, int32_t n_d, const double* W,
+                                  const double* u_lim, const double* x_cur, const int32_t* n_done, const double* X_exec,
+                                  const double* U_exec, const double* J_exec, const double* min_sep, const double* dist_left,
+                                  const double* U_next, const double* X_next) {
+    const int32_t rc = check_desc(desc);
+    if (rc) return rc;
+    if (!X || !U || !x_cur || !n_done || !X_exec || !U_exec || !J_exec || !min_sep || !dist_left || !U_next || !X_next)
+        return fail(DPILQR_EINVAL, "%s: NULL pointer", who);
+    if (h < 1 || h > desc->T) return fail(DPILQR_EINVAL, "%s: h=%d, a round executes 1 .. T = %d steps", who, h, desc->T);
+    if (L < 1) return fail(DPILQR_EINVAL, "%s: L=%d", who, L);
+    if (n_d < 1 || n_d > desc->n_s) return fail(DPILQR_EINVAL, "%s: n_d=%d, an agent has n_s = %d states", who, n_d, desc->n_s);
+    if (n_scen < desc->B) return fail(DPILQR_EINVAL, "%s: n_scen=%d for B = %d items", who, n_scen, desc->B);
+    uintptr_t dbls = 0;
+    for (const double* p : {X, U, K, W, u_lim, x_cur, X_exec, U_exec, J_exec, min_sep, dist_left, U_next, X_next}) dbls |= reinterpret_cast<uintptr_t>(p);
+    const uintptr_t ints = reinterpret_cast<uintptr_t>(scen) | reinterpret_cast<uintptr_t>(n_done);
+    return dbls % alignof(double) == 0 && ints % alignof(int32_t) == 0
+               ? DPILQR_OK : fail(DPILQR_EINVAL, "%s: a device pointer is not aligned to its element type", who);
+}
+
+int32_t dpilqr_policy_advance(const dpilqr_batch_desc* desc, const double* X, const double* U, const double* K, int32_t h,
+                              const int32_t* scen, int32_t n_scen, int32_t L, int32_t n_d, const double* W, const double* u_lim,
+                              double* x_cur, int32_t* n_done, double* X_exec, double* U_exec, double* J_exec, double* min_sep,
+                              double* dist_left, double* U_next, double* X_next, void* stream) {
+    const int32_t rc = check_advance_args("policy_advance", desc, X, U, K, h, scen, n_scen, L, n_d, W, u_lim, x_cur, n_done, X_exec,
+                                          U_exec, J_exec, min_sep, dist_left, U_next, X_next);
+    return rc ? rc : launch_policy_advance(*desc, X, U, K, 0, nullptr, h, scen, n_scen, L, n_d, W, u_lim, x_cur, n_done, X_exec, U_exec,
+                                           J_exec, min_sep, dist_left, U_next, X_next, as_stream(stream));
+}
+
+int32_t dpilqr_policy_advance_dec(const dpilqr_batch_desc* desc, const double* X, const double* U_ff, const double* Kc,
+                                  int32_t kc_max, const uint64_t* nbr_bits, int32_t h, const int32_t* scen, int32_t n_scen,
+                                  int32_t L, int32_t n_d, const double* W, const double* u_lim, double* x_cur, int32_t* n_done,
+                                  double* X_exec, double* U_exec, double* J_exec, double* min_sep, double* dist_left,
+                                  double* U_next, double* X_next, void* stream) {
+    const int32_t rc = check_advance_args("policy_advance_dec", desc, X, U_ff, Kc, h, scen, n_scen, L, n_d, W, u_lim, x_cur, n_done,
+                                          X_exec, U_exec, J_exec, min_sep, dist_left, U_next, X_next);
+    if (rc) return rc;
+    if ((Kc && !nbr_bits) || reinterpret_cast<uintptr_t>(nbr_bits) % alignof(uint64_t) != 0)
+        return fail(DPILQR_EINVAL, "policy_advance_dec: nbr_bits is a NULL pointer or not aligned to its element type");
+    if (kc_max < 1 || kc_max > desc->k)
+        return fail(DPILQR_EUNSUPPORTED, "policy_advance_dec: kc_max=%d, a neighbourhood has 1 .. k = %d members", kc_max, desc->k);
+    return launch_policy_advance(*desc, X, U_ff, Kc, kc_max, nbr_bits, h, scen, n_scen, L, n_d, W, u_lim, x_cur, n_done, X_exec, U_exec,
+                                 J_exec, min_sep, dist_left, U_next, X_next, as_stream(stream));
+}
+
 int32_t dpilqr_alphas(double* alphas_host) {
     if (!alphas_host) return fail(DPILQR_EINVAL, "alphas: NULL pointer");
     alpha_table(alphas_host);

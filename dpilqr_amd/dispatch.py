@@ -275,6 +275,14 @@ class DistributedPolicy:
         self._masks_checked = self.bits
         return r
 
+    def advance(self, h, state, scen=None, W=None, u_lim=None, n_d=2):
+        """Execute h steps of every scenario's policy on the plant state kept in `state` and shift the plan
+        (ProblemBatch.policy_advance_dec on the full problem): the step between two solves of a receding-horizon loop."""
+        r = self.batch().policy_advance_dec(self.X_dec, self.U_ff, self.Kc, self.bits, h, state, scen=scen, W=W, u_lim=u_lim, n_d=n_d,
+                                            masks_checked=self._masks_checked)
+        self._masks_checked = self.bits
+        return r
+
 
 def solve_scenarios_distributed(problem, X, U, radius, xf=None, window=None, concurrent=True, ignore_ids=None, device_out=False,
                                 shard=None, audit=False, desc=None, policy=False, policy_mu=0.0, **kwargs):

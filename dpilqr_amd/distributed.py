@@ -291,3 +291,120 @@ def solve_rhc_scenarios(problem, x0, N, radius, xf=None, U0=None, centralized=Fa
     if want_rows:
         rows.extend(row_log)
     return out
+
+
+def solve_rhc_closed_loop(problem, x0, N, radius=None, xf=None, U0=None, centralized=True, feedback=True, W=None, u_lim=None,
+                          policy_mu=0.0, n_d=2, step_size=1, dist_converge=None, J_converge=None, max_steps=None, window=None,
+                          **kwargs):
+    """The receding-horizon loop on a REAL plant, for S scenarios in lock step: plan, execute step_size steps of the plan's
+    feedback policy under a disturbance and actuator limits, re-plan from where the plant ended up.  solve_rhc and
+    solve_rhc_scenarios keep the reference's ideal plant (xi = X[step_size]); here every round is one batched solve over the
+    scenarios still running -- ProblemBatch.solve and, with feedback, one backward_pass(X, U, policy_mu) at the solution when
+    centralized, solve_scenarios_distributed(policy=feedback, policy_mu=...) otherwise -- followed by ONE launch of
+    ProblemBatch.policy_advance / policy_advance_dec, which executes u = U[t] + K[t] (x - X[t]) (feedback=False: u = U[t])
+    from every scenario's plant state, appends to the executed trajectories and shifts the warm start (distributed.py:184-185
+    with the plant's state in front).  Only the stopping flags come to the host each round, by solve_rhc's rules: the planned
+    J >= J_converge, or any agent further than dist_converge from its goal over n_d coordinates.
+
+    x0 (S, n_x); xf (S, n_x) goals (default: the problem's own); U0 (S, N, n_u) warm starts (default: drawn as solve_rhc draws
+    them); W (S, L, n_x) additive disturbance on the plant, read at a scenario's own executed step; u_lim (2, n_u) control
+    limits; radius: the graph threshold of the distributed solve.  The capacity L = max_steps (default: W's length) bounds the
+    executed steps as t_diverge bounds solve_rhc: a scenario that reaches it without meeting its criterion has converged =
+    False.  kwargs: n_lqr_iter, tol, t_kill reach every solve.
+    Returns a dict: X, U -- lists of S host arrays (n_s + 1, n_x), (n_s, n_u) of the executed lengths --, J (S,) the realised
+    cost (stage costs of the executed points plus the terminal cost of the final state), min_sep (S,), goal_dist (S, k),
+    converged (S,), n_rounds (S,).
+    Not built: clusters of n_x > 60, fp32, shard=, ignore_ids.  Device problems only."""
+    import torch
+    from .batch import ProblemBatch
+    from .device import to_dev
+    from .dispatch import device_constants
+    from .lowering import describe, is_lowerable
+    if not is_lowerable(problem):
+        raise NotImplementedError("solve_rhc_closed_loop runs the plant on the device and needs a problem built from the recognised "
+                                  "plugin types: this one contains host plugins, whose dynamics and cost only exist as Python "
+                                  "callables")
+    if (J_converge is None) == (dist_converge is None):
+        raise ValueError("Must either specify a convergence cost or distance")
+    n_x, n_u = problem.dynamics.n_x, problem.dynamics.n_u
+    if n_x > 60:
+        raise ValueError(f"solve_rhc_closed_loop serves problems up to n_x = 60, this one has n_x = {n_x}")
+    if not centralized and radius is None:
+        raise ValueError("solve_rhc_closed_loop: the distributed solve needs the graph's radius")
+    x0 = np.asarray(x0, dtype=np.float64).reshape(-1, n_x)
+    S = x0.shape[0]
+    if W is not None:
+        W = np.asarray(W, dtype=np.float64) if not isinstance(W, torch.Tensor) else W
+        if W.ndim != 3 or W.shape[0] != S or W.shape[2] != n_x:
+            raise ValueError(f"solve_rhc_closed_loop: W has shape {tuple(W.shape)}, expected ({S}, L, {n_x})")
+    L = int(max_steps) if max_steps is not None else (int(W.shape[1]) if W is not None else None)
+    if L is None:
+        raise ValueError("solve_rhc_closed_loop: max_steps (or a disturbance W, whose length it defaults to) bounds the executed steps")
+    if L < 1 or (W is not None and W.shape[1] != L):
+        raise ValueError(f"solve_rhc_closed_loop: max_steps = {L} with W of shape {None if W is None else tuple(W.shape)}")
+    h = int(step_size)
+    if not 1 <= h <= N:
+        raise ValueError(f"solve_rhc_closed_loop: step_size = {step_size}, a round executes 1 .. N = {N} steps")
+    d = describe(problem)
+    k, dt = d["k"], d["dt"]
+    n_s = n_x // k
+    if not 1 <= n_d <= n_s:
+        raise ValueError(f"solve_rhc_closed_loop: n_d = {n_d}, an agent has {n_s} states")
+    solve_kw = solve_kwargs(kwargs, "solve_rhc_closed_loop")
+    xf_h = np.broadcast_to(d["xf"], (S, n_x)).copy() if xf is None else np.asarray(xf, dtype=np.float64).reshape(S, n_x)
+    U_h = np.stack([np.random.rand(N, n_u) * 0.01 for _ in range(S)]) if U0 is None else np.array(U0, dtype=np.float64).reshape(S, N, n_u)
+    xf_d = to_dev(xf_h)
+    c = device_constants(d)
+
+    def batch(idx):
+        return ProblemBatch(c["model"], c["n_dims"], xf_d if idx is None else xf_d[idx], c["Q"], c["R"], c["Qf"], d["radius"], dt, N,
+                            w_ref=d["w_ref"], w_prox=d["w_prox"], B=S if idx is None else len(idx), hints=(k, n_s, n_u // k, c["word"]))
+
+    full = batch(None)
+    state = full.advance_state(x0, L)
+    state["U_next"].copy_(to_dev(U_h))
+    W_d = None if W is None else to_dev(W)
+    lim_d = None if u_lim is None else to_dev(np.asarray(u_lim, dtype=np.float64) if not isinstance(u_lim, torch.Tensor) else u_lim)
+    dev = xf_d.device
+    state["dist_left"].copy_(torch.linalg.vector_norm((state["x_cur"] - xf_d).reshape(S, k, n_s)[:, :, :n_d], dim=2))
+    J = torch.full((S,), float("inf"), dtype=torch.float64, device=dev)
+
+    def flags(idx):      # one small device -> host read per round: (keeps going, has room) per scenario
+        crit = (J[idx] >= J_converge) if J_converge else (state["dist_left"][idx] > dist_converge).any(dim=1)
+        return torch.stack([crit, state["n_done"][idx] < L]).cpu().numpy()
+
+    converged = np.ones(S, dtype=bool)
+    n_rounds = np.zeros(S, dtype=np.int64)
+    go, room = flags(torch.arange(S, device=dev))
+    active = np.nonzero(go & room)[0]
+    first = True
+    while active.size:
+        ia = torch.as_tensor(active, device=dev)
+        scen = ia.to(torch.int32)
+        if centralized:
+            pb = batch(ia)
+            r = pb.solve(state["x_cur"][ia], state["U_next"][ia], window=window, **solve_kw)
+            K = pb.backward_pass(r["X"], r["U"], float(policy_mu))[0] if feedback else None
+            pb.policy_advance(r["X"], r["U"], K, h, state, scen=scen, W=W_d, u_lim=lim_d, n_d=n_d)
+            J[ia] = r["J"]
+        else:
+            Xin = state["x_cur"][ia][:, None, :] if first else state["X_next"][ia]
+            Xa, Ua, Ja, info = solve_scenarios_distributed(problem, Xin, state["U_next"][ia], radius, xf=xf_d[ia], window=window,
+                                                           device_out=True, desc=d, policy=bool(feedback), policy_mu=float(policy_mu),
+                                                           **solve_kw)
+            if feedback:
+                info["policy"].advance(h, state, scen=scen, W=W_d, u_lim=lim_d, n_d=n_d)
+            else:
+                batch(ia).policy_advance_dec(Xa, Ua, None, None, h, state, scen=scen, W=W_d, u_lim=lim_d, n_d=n_d)
+            J[ia] = Ja
+        first = False
+        n_rounds[active] += 1
+        go, room = flags(ia)
+        converged[active[go & ~room]] = False
+        active = active[go & room]
+    n_done = state["n_done"].cpu().numpy()
+    X_exec, U_exec = state["X_exec"].cpu().numpy(), state["U_exec"].cpu().numpy()
+    J_term = full.cost(state["x_cur"][:, None, :], torch.zeros((S, 1, n_u), dtype=torch.float64, device=dev), terminal=True)[:, 0]
+    return dict(X=[X_exec[s, :n_done[s] + 1].copy() for s in range(S)], U=[U_exec[s, :n_done[s]].copy() for s in range(S)],
+                J=(state["J_exec"] + J_term).cpu().numpy(), min_sep=state["min_sep"].cpu().numpy(),
+                goal_dist=state["dist_left"].cpu().numpy(), converged=converged, n_rounds=n_rounds)

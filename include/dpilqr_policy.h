@@ -87,4 +87,47 @@ int32_t dpilqr_dispatch_stitch_policy(int32_t S, int32_t k, int32_t n_s, int32_t
                                       const dpilqr_bucket_results* results, const dpilqr_bucket_gains* gains, const double* X_dec,
                                       double* Kc, double* U_ff, void* stream);
 
+/* The step between two solves of a receding-horizon loop: execute h steps of each running scenario's CURRENT plan on the plant
+ * and do the loop's bookkeeping, in one launch.  `desc` describes the B items of this round -- the scenarios still running,
+ * compact -- with their plans X[B][T+1][n_x], U[B][T][n_u] and gains K[B][T][n_u][n_x] (K NULL: the plan is executed open loop).
+ * The loop's state is indexed by SCENARIO: item j is scenario s = scen[j] (scen NULL: s = j) of n_scen; it has executed
+ * n_done[s] steps so far out of a capacity of L.  Per item j:
+ *     he = min(h, L - n_done[s])                            never past the capacity
+ *     x  = x_cur[s];  g = n_done[s]                         x_cur[n_scen][n_x], n_done[n_scen]
+ *     if g == 0: min_sep[s] = separation(x)                 the start state counts (a caller sets min_sep to +inf otherwise)
+ *     for i = 0 .. he-1:
+ *         u = U[j][i] + K[j][i] (x - X[j][i])               the sum over columns 0 .. n_x-1 in that order, as dpilqr_policy_rollout
+ *         u = u < lo ? lo : (u > hi ? hi : u)   per entry   u_lim[2][n_u], NULL: no limits.  A NaN stays a NaN.
+ *         X_exec[s][g+i] = x;  U_exec[s][g+i] = u           X_exec[n_scen][L+1][n_x], U_exec[n_scen][L][n_u]
+ *         J_exec[s] = J_exec[s] + cost(x, u)                ONE addition per step, in time order; the stage cost summed as the
+ *                                                           rollout sums it (pairs in combinations order, agents in order)
+ *         x = step(x, u)   [+ W[s][g+i]]                    W[n_scen][L][n_x] additive disturbance, NULL: none
+ *         min_sep[s] = min(min_sep[s], separation(x))       the distance dpilqr_policy_rollout's min_sep measures (quirk Q5)
+ *     X_exec[s][g+he] = x;  x_cur[s] = x;  n_done[s] = g + he
+ *     dist_left[s][a] = |x - xf| over agent a's first n_d coordinates          dist_left[n_scen][k]
+ *     U_next[s][t] = U[j][t+he] for t < T-he, 0 beyond                         U_next[n_scen][T][n_u]: the next warm start
+ *     X_next[s][0] = x;  X_next[s][t] = X[j][min(t+he, T)] for 1 <= t <= T     X_next[n_scen][T+1][n_x]
+ * The step, the cost and the separation are dpilqr_policy_rollout's, statement for statement: X_exec / U_exec equal the prefix
+ * of that rollout's Xs / Us bit for bit, and two calls of h1 and h2 steps equal one of h1 + h2 (on the shifted plan).
+ * U_next / X_next must not alias U / X.  Scenarios not named in scen are not touched; an entry of scen outside [0, n_scen) is
+ * skipped; scen must not name a scenario twice.
+ * DPILQR_EINVAL: a NULL among desc, X, U, x_cur, n_done, X_exec, U_exec, J_exec, min_sep, dist_left, U_next, X_next; h < 1 or
+ * h > T; L < 1; n_d < 1 or n_d > n_s; n_scen < B; a pointer not aligned to its element type.  DPILQR_EUNSUPPORTED, before
+ * any launch: n_x > 60 or k > 20.  B = 0: DPILQR_OK, nothing is launched.  fp64 only.  Enqueue only, nothing is allocated.
+ * One workgroup holds floor(256 / k) ITEMS (csrc/policy_advance.hpp). */
+int32_t dpilqr_policy_advance(const dpilqr_batch_desc* desc, const double* X, const double* U, const double* K, int32_t h,
+                              const int32_t* scen, int32_t n_scen, int32_t L, int32_t n_d, const double* W, const double* u_lim,
+                              double* x_cur, int32_t* n_done, double* X_exec, double* U_exec, double* J_exec, double* min_sep,
+                              double* dist_left, double* U_next, double* X_next, void* stream);
+
+/* The same step under a DISTRIBUTED solution's policy: X is the stitched X_dec, the nominal U_ff[B][T][n_u], the gains
+ * Kc[B][T][k][n_c][kc_max * n_s] and the masks nbr_bits[B][k] as dpilqr_policy_rollout_dec defines them (members lowest bit
+ * first; columns at and past kc_i * n_s are never read; the masks are the caller's contract).  Kc NULL: u = U_ff (open loop:
+ * pass U_dec), nbr_bits may then be NULL too.  Further DPILQR_EUNSUPPORTED: kc_max outside 1 .. k. */
+int32_t dpilqr_policy_advance_dec(const dpilqr_batch_desc* desc, const double* X, const double* U_ff, const double* Kc,
+                                  int32_t kc_max, const uint64_t* nbr_bits, int32_t h, const int32_t* scen, int32_t n_scen,
+                                  int32_t L, int32_t n_d, const double* W, const double* u_lim, double* x_cur, int32_t* n_done,
+                                  double* X_exec, double* U_exec, double* J_exec, double* min_sep, double* dist_left,
+                                  double* U_next, double* X_next, void* stream);
+
 #endif /* DPILQR_POLICY_H */
