@@ -46,7 +46,7 @@ WAVE_TABLE = instantiation_table("tu_forward.hip", "DPILQR_TRY_WAVE")        # k
 TEAM_TABLE = instantiation_table("tu_lsteam.hip", "DPILQR_TRY_LSTEAM")       # k_linesearch_team<MODEL, KA>
 # U0 noise per model: 0.05 is test_fuzz_shapes_against_oracle's.  Raised for CarDynamics3D and BikeDynamics5D, where the oracle
 # alone then rejects the first candidate on 10 % of the items and more (profiles/linesearch_oracle_sensitivity.txt).
-U0_NOISE = {0: 0.05, 3: 0.05, 4: 0.05, 2: 0.5, 5: 0.05, 1: 0.05, 6: 0.05, 7: 0.05, BIKE: 2.0}
+U0_NOISE = {0: 0.05, 3: 0.05, 4: 0.05, 2: 0.5, 5: 0.05, 1: 0.05, 6: 0.05, 7: 0.05, 8: 0.05, BIKE: 2.0}
 # The double integrators and the linearised human are LINEAR, the twelve-state quadcopter is held near hover: with radius 0.6
 # their line search from mu = 1 all but always accepts the first candidate, at any U0 noise -- only the proximity cost bends the
 # problem.  Clusters of these models (the double integrator up to seven agents: beyond, 0.6 is enough) get WIDE_RADIUS, so that
