@@ -103,7 +103,17 @@ EXT_SIGNATURES = {
     "dpilqr_policy_advance_dec": (i32, [_DP, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
 }
 
-MAX_AGENTS = 64
+# ... and of include/dpilqr_swarm.h: teams of 64 < k <= MAX_TEAM agents.  The three dispatch entries take their narrow
+# counterparts' arguments plus n_words (before the stream)
+SWARM_SIGNATURES = {
+    "dpilqr_dispatch_graph_wide": (i32, SIGNATURES["dpilqr_dispatch_graph"][1][:-1] + [i32, vp]),
+    "dpilqr_dispatch_gather_wide": (i32, SIGNATURES["dpilqr_dispatch_gather"][1][:-1] + [i32, vp]),
+    "dpilqr_dispatch_stitch_wide": (i32, SIGNATURES["dpilqr_dispatch_stitch"][1][:-1] + [i32, vp]),
+    "dpilqr_rollout_wide": (i32, [_DP, vp, vp, vp, vp, vp, vp, vp]),
+}
+
+MAX_AGENTS = 64          # DPILQR_MAX_AGENTS: agents of a sub-problem (cluster), and of a problem on the one-word entries
+MAX_TEAM = 256           # DPILQR_MAX_TEAM: agents of a problem on the wide entries (include/dpilqr_swarm.h)
 
 
 class BucketResults(C.Structure):
@@ -128,7 +138,7 @@ def load():
             raise ImportError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                               "(hipcc --offload-arch=gfx950).  dpilqr_amd has no CPU fallback.")
         lib = C.CDLL(str(LIB_PATH))
-        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **SWARM_SIGNATURES}.items():
             fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

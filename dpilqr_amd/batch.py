@@ -227,6 +227,22 @@ class ProblemBatch:
         _lib.check(fn(self._d, ptr(x0), ptr(U), ptr(X), ptr(J), stream_handle()))
         return X, J
 
+    def rollout_wide(self, x0, U, trajectories=True):
+        """The rollout of a FULL team of up to 256 agents (dpilqr_rollout_wide, include/dpilqr_swarm.h): rollout's definition for
+        every item -- what J_full of a distributed solve of more than 64 agents is computed with -- plus min_sep and goal_dist as
+        policy_rollout defines them.  Returns a dict of device tensors: J (B,), min_sep (B,), goal_dist (B,k) and, with
+        trajectories=True, X (B,T+1,n_x).  Its sums have a fixed shape of their own: J agrees with rollout's to rounding, not bit
+        for bit, and is the same bits run after run.  fp64 only."""
+        if self.k > _lib.MAX_TEAM:
+            raise ValueError(f"rollout_wide serves teams of up to {_lib.MAX_TEAM} agents, this batch has k = {self.k}")
+        x0 = self._in(x0, (self.B, self.n_x)); U = self._in(U, (self.B, self.T, self.n_u))
+        out = dict(J=empty((self.B,)), min_sep=empty((self.B,)), goal_dist=empty((self.B, self.k)))
+        if trajectories:
+            out["X"] = empty((self.B, self.T + 1, self.n_x))
+        _lib.check(self._lib.dpilqr_rollout_wide(self._d, ptr(x0), ptr(U), ptr(out.get("X")), ptr(out["J"]), ptr(out["min_sep"]),
+                                                 ptr(out["goal_dist"]), stream_handle()))
+        return out
+
     def make_tiles(self, X, U, tiles=None):
         """linearize + quadraticize at every (X[t],U[t]) -> packed tile records (B,T+1,stride)."""
         X = self._in(X, (self.B, self.T + 1, self.n_x)); U = self._in(U, (self.B, self.T, self.n_u))

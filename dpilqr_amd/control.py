@@ -63,7 +63,11 @@ class ilqrSolver:
     def _rollout(self, x0, U):
         U = np.asarray(U, dtype=np.float64); x0 = np.asarray(x0, dtype=np.float64).reshape(-1)
         if self.on_device:
-            X, J = self._pb(U.shape[0]).rollout(x0[None], U[None])
+            pb = self._pb(U.shape[0])
+            if pb.k > _lib.MAX_AGENTS:     # a full team of up to 256 agents (solve_distributed's J_full): the wide rollout
+                r = pb.rollout_wide(x0[None], U[None])
+                return r["X"][0].cpu().numpy(), float(r["J"].item())
+            X, J = pb.rollout(x0[None], U[None])
             return X[0].cpu().numpy(), float(J.item())
         X = np.zeros((U.shape[0] + 1, self.n_x)); X[0] = x0
         J = 0.0

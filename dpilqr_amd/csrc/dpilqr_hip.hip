@@ -71,10 +71,11 @@ int32_t check_family5(const dpilqr_batch_desc* d, bool f32) {
     return DPILQR_OK;
 }
 
-int32_t check_desc(const dpilqr_batch_desc* d) {
+// max_k: kMaxAgents for every entry but the full-team rollout (dpilqr_rollout_wide: 256)
+int32_t check_desc(const dpilqr_batch_desc* d, int max_k = kMaxAgents) {
     if (!d) return fail(DPILQR_EINVAL, "desc is NULL");
     if (d->B < 0 || d->k < 1 || d->T < 1) return fail(DPILQR_EINVAL, "bad sizes B=%d k=%d T=%d", d->B, d->k, d->T);
-    if (d->k > kMaxAgents) return fail(DPILQR_EUNSUPPORTED, "k=%d agents per sub-problem exceeds %d", d->k, kMaxAgents);
+    if (d->k > max_k) return fail(DPILQR_EUNSUPPORTED, "k=%d agents per sub-problem exceeds %d", d->k, max_k);
     if (family_nc(d->n_s) != d->n_c)
         return fail(DPILQR_EINVAL, "(n_s,n_c)=(%d,%d) is not a model family; expected (3,2),(4,2),(5,2),(6,3),(12,4)", d->n_s, d->n_c);
     if (d->B > 0 && (!d->model || !d->n_dims || !d->xf || !d->Q || !d->R || !d->Qf || !d->radius))   // an empty batch owns nothing
@@ -660,6 +661,17 @@ int32_t dpilqr_rollout(const dpilqr_batch_desc* desc, const double* x0, const do
     SolveState S{};
     return launch_forward(*desc, kModeRollout, x0, X, const_cast<double*>(U), nullptr, nullptr, nullptr, 1, nullptr,
                           nullptr, J, S, nullptr, nullptr, desc->B, as_stream(stream));
+}
+
+int32_t dpilqr_rollout_wide(const dpilqr_batch_desc* desc, const double* x0, const double* U, double* X, double* J,
+                            double* min_sep, double* goal_dist, void* stream) {
+    const int32_t rc = check_desc(desc, 256);
+    if (rc) return rc;
+    if (!x0 || !U || !J) return fail(DPILQR_EINVAL, "rollout_wide: NULL pointer");
+    uintptr_t dbls = 0;      // check_desc's alignment rule
+    for (const double* p : {x0, U, (const double*)X, (const double*)J, (const double*)min_sep, (const double*)goal_dist}) dbls |= reinterpret_cast<uintptr_t>(p);
+    if (dbls % alignof(double) != 0) return fail(DPILQR_EINVAL, "rollout_wide: a device pointer is not aligned to its element type");
+    return launch_rollout_wide(*desc, x0, U, X, J, min_sep, goal_dist, as_stream(stream));
 }
 
 int32_t dpilqr_backward_pass_tiles(int32_t B, int32_t T, int32_t n_x, int32_t n_u, const double* tiles,

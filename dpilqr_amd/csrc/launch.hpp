@@ -6,7 +6,8 @@
 // tu_team.hip (the fused wavefront sweeps with a helper wavefront per item), tu_inprod.hip (the wavefront sweeps with in-sweep
 // production), tu_bike.hip (the same for the five-state family, BikeDynamics5D), tu_lsteam.hip (the line search with two
 // wavefronts per item), tu_frontend.hip (the device-side dispatch front / back end), tu_policy.hip (the closed-loop ensemble rollouts),
-// tu_policy_large.hip (the same for n_x > 60), tu_policy_advance.hip (the receding-horizon advance) and dpilqr_hip.hip (the C ABI and the solve loop).
+// tu_policy_large.hip (the same for n_x > 60), tu_policy_advance.hip (the receding-horizon advance), tu_rollout_wide.hip (the
+// full-team rollout for up to 256 agents) and dpilqr_hip.hip (the C ABI and the solve loop).
 // No device code crosses a file boundary.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -230,6 +231,11 @@ int32_t launch_policy_advance(const dpilqr_batch_desc& D, const double* X, const
 int32_t launch_policy_rollout_large(const dpilqr_batch_desc& D, const double* X, const double* U, const double* K, int32_t n_samples,
                                     const double* x0s, const double* W, const double* u_lim, double* Xs, double* Us, double* J,
                                     double* min_sep, double* goal_dist, hipStream_t st);
+
+// ---- tu_rollout_wide.hip: dpilqr_rollout's definition for a full team of up to 256 agents, one workgroup per item
+// (rollout_wide.hpp); X, min_sep, goal_dist may be null; enqueue only
+int32_t launch_rollout_wide(const dpilqr_batch_desc& D, const double* x0, const double* U, double* X, double* J, double* min_sep,
+                            double* goal_dist, hipStream_t st);
 
 // ---- tu_big.hip: large clusters (n_x > 60) in fp64, any size in fp32 (BASELINE config 5's tolerance study)
 int64_t riccati_big_scratch_elems(int n, int m);   // per sub-problem in flight, in elements of the arithmetic type

@@ -5,6 +5,7 @@
 
 #include "dpilqr_hip.h"
 #include "frontend.hpp"
+#include "frontend_wide.hpp"
 #include "launch.hpp"
 
 using namespace dpilqr;
@@ -141,6 +142,74 @@ int32_t dpilqr_dispatch_scatter_rows(int64_t n_rows_total, int32_t k, int32_t n_
     if (n_rows_total == 0) return DPILQR_OK;
     hipLaunchKernelGGL(k_scatter_rows, dim3((unsigned)n_rows_total), dim3(128), 0, as_stream(stream), n_rows_total, k, n_s, n_c, T,
                        rows, row_len, X_dec, U_dec);
+    HIP_TRY(hipGetLastError());
+    return DPILQR_OK;
+}
+
+// ---- teams of 64 < k <= 256 agents (frontend_wide.hpp): the narrow entries' arguments plus n_words = ceil(k / 64)
+static int32_t check_wide(const char* who, int32_t k, int32_t n_words) {
+    if (k < 1 || k > kWideMaxAgents) return fail(DPILQR_EINVAL, "%s: k=%d, the wide entries serve 1 .. %d agents", who, k, kWideMaxAgents);
+    if (n_words != (k + 63) / 64) return fail(DPILQR_EINVAL, "%s: n_words=%d, k=%d agents take ceil(k / 64) = %d words", who, n_words, k, (k + 63) / 64);
+    return DPILQR_OK;
+}
+
+int32_t dpilqr_dispatch_graph_wide(int32_t S, int32_t N, int32_t k, int32_t n_s, const double* X, const double* radius,
+                                   int64_t radius_stride, const int32_t* ignore, uint64_t* bits, int32_t* rep, int32_t* size,
+                                   int32_t* order, int32_t* slot, int32_t* bucket_start, int32_t* bucket_count, int32_t n_words,
+                                   void* stream) {
+    const int32_t rc = check_wide("dispatch_graph_wide", k, n_words);
+    if (rc) return rc;
+    if (S < 0 || N < 1 || n_s < 2 || !X || !radius || !bits || !rep || !size || !order || !slot || !bucket_start || !bucket_count)
+        return fail(DPILQR_EINVAL, "dispatch_graph_wide: bad argument");
+    hipStream_t st = as_stream(stream);
+    if (S == 0) {
+        HIP_TRY(hipMemsetAsync(bucket_start, 0, sizeof(int32_t) * (k + 1), st));
+        HIP_TRY(hipMemsetAsync(bucket_count, 0, sizeof(int32_t) * (k + 1), st));
+        return DPILQR_OK;
+    }
+    const size_t lds_graph = graph_wide_lds_bytes(N, k), lds_sort = sizeof(int32_t) * (k + 1) * kWideSortThreads;
+    {   // both above 64 KiB for the largest teams: ask before anything of this call is queued
+        int32_t rc_lds = allow_lds(k_graph_bits_wide, lds_graph);
+        if (!rc_lds) rc_lds = allow_lds(k_bucket_sort_wide, lds_sort);
+        if (rc_lds) return rc_lds;
+    }
+    const int64_t n = (int64_t)S * k;
+    const unsigned long long* b = reinterpret_cast<const unsigned long long*>(bits);
+    hipLaunchKernelGGL(k_graph_bits_wide, dim3((unsigned)S), dim3(kWideThreads), lds_graph, st, S, N, k, n_s, n_words, X, radius,
+                       radius_stride, reinterpret_cast<unsigned long long*>(bits));
+    hipLaunchKernelGGL(k_dedup_wide, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, S, k, n_words, b, ignore, rep, size);
+    hipLaunchKernelGGL(k_bucket_sort_wide, dim3(1), dim3(kWideSortThreads), lds_sort, st, S, k, rep, size, order, bucket_start,
+                       bucket_count, slot);
+    HIP_TRY(hipGetLastError());
+    return DPILQR_OK;
+}
+
+int32_t dpilqr_dispatch_gather_wide(int32_t k, int32_t n_s, int32_t n_c, int32_t T, int32_t n_rows, int32_t kc, const int32_t* order,
+                                    int32_t first, int32_t count, const uint64_t* bits, const double* X, const double* U,
+                                    const double* xf, int64_t xf_stride, double* x0_out, double* xf_out, double* U_out,
+                                    int32_t* members, int32_t n_words, void* stream) {
+    const int32_t rc = check_wide("dispatch_gather_wide", k, n_words);
+    if (rc) return rc;
+    if (kc < 1 || kc > k || count < 0 || first < 0 || !order || !bits || !X || !U || !xf || !x0_out || !xf_out || !U_out)
+        return fail(DPILQR_EINVAL, "dispatch_gather_wide: bad argument");
+    if (kc > kFrontMaxAgents) return fail(DPILQR_EINVAL, "dispatch_gather_wide: kc=%d, sub-problems have at most %d agents", kc, kFrontMaxAgents);
+    if (count == 0) return DPILQR_OK;
+    hipLaunchKernelGGL(k_gather_bucket_wide, dim3(count), dim3(128), 0, as_stream(stream), k, n_s, n_c, T, n_rows, kc, n_words, order,
+                       first, count, reinterpret_cast<const unsigned long long*>(bits), X, U, xf, xf_stride, x0_out, xf_out, U_out,
+                       members);
+    HIP_TRY(hipGetLastError());
+    return DPILQR_OK;
+}
+
+int32_t dpilqr_dispatch_stitch_wide(int32_t S, int32_t k, int32_t n_s, int32_t n_c, int32_t T, const uint64_t* bits,
+                                    const int32_t* rep, const int32_t* size, const int32_t* slot,
+                                    const dpilqr_bucket_results* results, double* X_dec, double* U_dec, int32_t n_words, void* stream) {
+    const int32_t rc = check_wide("dispatch_stitch_wide", k, n_words);
+    if (rc) return rc;
+    if (S < 0 || !bits || !rep || !size || !slot || !results || !X_dec || !U_dec) return fail(DPILQR_EINVAL, "dispatch_stitch_wide: bad argument");
+    if (S == 0) return DPILQR_OK;
+    hipLaunchKernelGGL(k_stitch_wide, dim3((unsigned)((int64_t)S * k)), dim3(128), 0, as_stream(stream), S, k, n_s, n_c, T, n_words,
+                       reinterpret_cast<const unsigned long long*>(bits), rep, size, slot, to_internal(results), X_dec, U_dec);
     HIP_TRY(hipGetLastError());
     return DPILQR_OK;
 }

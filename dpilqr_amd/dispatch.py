@@ -112,14 +112,24 @@ class ScenarioFrontEnd:
     section 7, csrc/frontend.hpp): interaction graphs as bit masks, one representative per distinct neighbourhood (the
     reference solves one sub-problem per agent: quirk Q11), a stable sort of the representatives by cluster size, the
     gathered inputs of every size's sub-problems, and the stitching of the owners' columns.  Only the k + 1 bucket counts
-    come back to the host (they size the launches)."""
+    come back to the host (they size the launches).
 
-    def __init__(self, d, X, U, radius, xf, ignore=None):
+    Teams of 64 < k <= 256 agents take the wide entries (include/dpilqr_swarm.h, csrc/frontend_wide.hpp): a neighbourhood is
+    n_words = ceil(k / 64) words and `bits` is (S*k, n_words); k <= 64 takes the one-word entries and `bits` is (S*k,), as ever
+    (wide=True puts such a team on the wide entries with n_words = 1: the same arrays, bit for bit).
+    A cluster (sub-problem) has at most 64 agents in either form: a populated cluster size beyond that is a ValueError before any
+    solve.  Not built for wide teams: stitch_policy, pack_rows / scatter_rows (policy=True, shard=)."""
+
+    def __init__(self, d, X, U, radius, xf, ignore=None, wide=None):
         self.lib = _lib.load()
         self.d = d
         k = self.k = d["k"]
-        if k > _lib.MAX_AGENTS:
-            raise ValueError(f"at most {_lib.MAX_AGENTS} agents per problem (one bit per agent)")
+        if k > _lib.MAX_TEAM:
+            raise ValueError(f"at most {_lib.MAX_TEAM} agents per problem, this one has {k}")
+        self.wide = k > _lib.MAX_AGENTS if wide is None else bool(wide)      # wide=True: a small team on the wide entries
+        if k > _lib.MAX_AGENTS and not self.wide:
+            raise ValueError(f"{k} agents need the wide entries (wide=False serves at most {_lib.MAX_AGENTS})")
+        self.n_words = nw = (k + 63) // 64
         self.X = to_dev(X).contiguous(); self.U = to_dev(U).contiguous()
         self.S, self.N = int(self.X.shape[0]), int(self.X.shape[1])
         self.T = int(self.U.shape[1])
@@ -131,14 +141,21 @@ class ScenarioFrontEnd:
         if ignore is not None and any(ignore):
             ign = to_dev(np.asarray(ignore, dtype=np.int32), torch.int32)
         n = max(S * k, 1)
-        self.bits = empty((n,), torch.int64)
+        self.bits = empty((n, nw) if self.wide else (n,), torch.int64)
         self.rep, self.size, self.order, self.slot = (empty((n,), torch.int32) for _ in range(4))
         self.bstart, self.bcount = empty((k + 1,), torch.int32), empty((k + 1,), torch.int32)
-        _lib.check(self.lib.dpilqr_dispatch_graph(S, self.N, k, self.n_s, ptr(self.X), ptr(rad), 1, ptr(ign), ptr(self.bits),
-                                                  ptr(self.rep), ptr(self.size), ptr(self.order), ptr(self.slot),
-                                                  ptr(self.bstart), ptr(self.bcount), stream_handle()))
+        graph_args = (S, self.N, k, self.n_s, ptr(self.X), ptr(rad), 1, ptr(ign), ptr(self.bits), ptr(self.rep), ptr(self.size),
+                      ptr(self.order), ptr(self.slot), ptr(self.bstart), ptr(self.bcount))
+        if self.wide:
+            _lib.check(self.lib.dpilqr_dispatch_graph_wide(*graph_args, nw, stream_handle()))
+        else:
+            _lib.check(self.lib.dpilqr_dispatch_graph(*graph_args, stream_handle()))
         self.counts = self.bcount.cpu().numpy()           # the one host read of the front end
         self.starts = self.bstart.cpu().numpy()
+        big = [(c, int(self.counts[c])) for c in range(_lib.MAX_AGENTS + 1, k + 1) if self.counts[c] > 0]
+        if big:
+            raise ValueError("a sub-problem has at most %d agents; this team has %s" % (
+                _lib.MAX_AGENTS, ", ".join(f"{n_} sub-problem{'s' if n_ != 1 else ''} of cluster size {c}" for c, n_ in big)))
         # per-agent parameters: one copy for every sub-problem when all agents are alike, gathered per item otherwise
         self.uniform_agents = all(bool((np.asarray(d[key]) == np.asarray(d[key])[0]).all()) for key in ("model", "n_dims", "Q", "R", "Qf"))
         if not self.uniform_agents:
@@ -155,9 +172,12 @@ class ScenarioFrontEnd:
         cnt = hi - lo
         x0 = empty((cnt, kc * ns)); xfb = empty((cnt, kc * ns)); U0 = empty((cnt, T, kc * nc))
         members = None if self.uniform_agents else empty((cnt, kc), torch.int32)
-        _lib.check(self.lib.dpilqr_dispatch_gather(k, ns, nc, T, self.N, kc, ptr(self.order), int(self.starts[kc]) + lo, cnt,
-                                                   ptr(self.bits), ptr(self.X), ptr(self.U), ptr(self.xf), k * ns, ptr(x0),
-                                                   ptr(xfb), ptr(U0), ptr(members), stream_handle()))
+        gather_args = (k, ns, nc, T, self.N, kc, ptr(self.order), int(self.starts[kc]) + lo, cnt, ptr(self.bits), ptr(self.X),
+                       ptr(self.U), ptr(self.xf), k * ns, ptr(x0), ptr(xfb), ptr(U0), ptr(members))
+        if self.wide:
+            _lib.check(self.lib.dpilqr_dispatch_gather_wide(*gather_args, self.n_words, stream_handle()))
+        else:
+            _lib.check(self.lib.dpilqr_dispatch_gather(*gather_args, stream_handle()))
         if self.uniform_agents:
             c = device_constants(d, kc)
             pb = ProblemBatch(c["model"], c["n_dims"], xfb, c["Q"], c["R"], c["Qf"], d["radius"], d["dt"], T, w_ref=d["w_ref"],
@@ -195,15 +215,24 @@ class ScenarioFrontEnd:
         U_dec = torch.zeros((S, T, k * nc), dtype=torch.float64, device=self.X.device)
         R = self.results_struct(solved)
         import ctypes as C
-        _lib.check(self.lib.dpilqr_dispatch_stitch(S, k, ns, nc, T, ptr(self.bits), ptr(self.rep), ptr(self.size), ptr(self.slot),
-                                                   C.addressof(R), ptr(X_dec), ptr(U_dec), stream_handle()))
+        stitch_args = (S, k, ns, nc, T, ptr(self.bits), ptr(self.rep), ptr(self.size), ptr(self.slot), C.addressof(R), ptr(X_dec),
+                       ptr(U_dec))
+        if self.wide:
+            _lib.check(self.lib.dpilqr_dispatch_stitch_wide(*stitch_args, self.n_words, stream_handle()))
+        else:
+            _lib.check(self.lib.dpilqr_dispatch_stitch(*stitch_args, stream_handle()))
         return X_dec, U_dec
+
+    def _narrow_only(self, what):
+        if self.wide:
+            raise ValueError(f"{what} is not built for teams of more than {_lib.MAX_AGENTS} agents (this one has {self.k})")
 
     def stitch_policy(self, solved, gains, X_dec):
         """The distributed feedback policy (dpilqr_dispatch_stitch_policy): solved as for stitch, gains {kc: K} the bucket's
         backward-pass gains (count, T, kc*n_c, kc*n_s), X_dec the stitched trajectories -> Kc (S, T, k, n_c, kc_max*n_s),
         U_ff (S, T, k*n_c), kc_max (the largest populated cluster size)."""
         import ctypes as C
+        self._narrow_only("stitch_policy")
         S, k, ns, nc, T = self.S, self.k, self.n_s, self.n_c, self.T
         kc_max = max(self.sizes(), default=1)
         Kc = empty((S, T, k, nc, kc_max * ns)); U_ff = empty((S, T, k * nc))
@@ -220,6 +249,7 @@ class ScenarioFrontEnd:
         """One row [s*k+i | X columns | U columns] per (scenario, agent) whose sub-problem is in `solved`; returns
         (rows or None, n_rows).  Rows beyond n_rows (up to pad_to) carry index -1."""
         import ctypes as C
+        self._narrow_only("pack_rows")
         S, k, ns, nc, T = self.S, self.k, self.n_s, self.n_c, self.T
         R = self.results_struct(solved)
         row_of = empty((max(S * k, 1),), torch.int32); n_rows = empty((1,), torch.int32)
@@ -303,6 +333,11 @@ def solve_scenarios_distributed(problem, X, U, radius, xf=None, window=None, con
             info["policy"], a DistributedPolicy; not with `shard` or `ignore_ids`
     returns X_dec (S, T+1, n_x), U_dec (S, T, n_u), J_full (S,), info (clusters as bit masks, counts) -- NumPy arrays, or
     device tensors with device_out=True; with `shard` the unstitched (front end, solved slices) pair instead.
+
+    Teams of 64 < k <= 256 agents are served too (multi-word masks, the full-team rollout ProblemBatch.rollout_wide for J_full):
+    info["cluster_bits"] is then (S, k, ceil(k / 64)) -- word w, bit b = agent 64 w + b -- instead of (S, k).  Every cluster still
+    has at most 64 agents and lies within the solver's own limits.  Not built for such teams: policy=True and shard= (each a
+    ValueError before any device work).
     """
     from .sharding import shard_bounds
     if policy and (shard is not None or ignore_ids):
@@ -310,6 +345,9 @@ def solve_scenarios_distributed(problem, X, U, radius, xf=None, window=None, con
                          "scenario needs its sub-problem's gains on this device)")
     d = desc if desc is not None else describe(problem)      # desc: the caller's description (its device constants are reused)
     k = d["k"]
+    if k > _lib.MAX_AGENTS and (policy or shard is not None):
+        raise ValueError(f"solve_scenarios_distributed: {'policy=True' if policy else 'shard='} is not built for teams of more than "
+                         f"{_lib.MAX_AGENTS} agents (this one has {k})")
     ignore = None
     if ignore_ids:
         ids = list(problem.ids)
@@ -375,7 +413,7 @@ def solve_scenarios_distributed(problem, X, U, radius, xf=None, window=None, con
         torch.cuda.synchronize()
         info["seconds"]["stitch_policy"] = pc() - t0
         info["policy"] = DistributedPolicy(d, fe.xf, X_dec, U_ff, Kc, fe.bits.reshape(S, k), kc_max)
-    info["cluster_bits"] = fe.bits.cpu().numpy().reshape(S, k)
+    info["cluster_bits"] = fe.bits.cpu().numpy().reshape((S, k, fe.n_words) if fe.wide else (S, k))
     if device_out:
         return X_dec, U_dec, J, info
     return X_dec.cpu().numpy(), U_dec.cpu().numpy(), J.cpu().numpy(), info
@@ -386,5 +424,8 @@ def full_rollout_cost(d, fe, U_dec):
     c = device_constants(d)
     full = ProblemBatch(c["model"], c["n_dims"], fe.xf, c["Q"], c["R"], c["Qf"], d["radius"], d["dt"], fe.T,
                         w_ref=d["w_ref"], w_prox=d["w_prox"], B=fe.S, hints=(d["k"], fe.n_s, fe.n_c, c["word"]))
-    _, J = full.rollout(fe.X[:, 0].contiguous(), U_dec)
+    x0 = fe.X[:, 0].contiguous()
+    if d["k"] > _lib.MAX_AGENTS:
+        return full.rollout_wide(x0, U_dec, trajectories=False)["J"]
+    _, J = full.rollout(x0, U_dec)
     return J

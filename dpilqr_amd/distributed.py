@@ -37,7 +37,8 @@ def solve_distributed(problem, X, U, radius, ignore_ids=None, pool=None, verbose
 
     Returns X_dec (N+1, n_x), U_dec (N, n_u), J_full, solve_info {id: (seconds, neighbourhood)}.
     `pool` is accepted for signature compatibility; the device batch takes its place.  `ignore_ids=None`
-    means "ignore nobody" (the reference raises TypeError there, quirk Q9)."""
+    means "ignore nobody" (the reference raises TypeError there, quirk Q9).  Teams of up to 256 agents are served (J_full of
+    more than 64 agents through ProblemBatch.rollout_wide); every neighbourhood must lie within the solver's own limits."""
     X = np.atleast_2d(np.asarray(X, dtype=np.float64)); U = np.asarray(U, dtype=np.float64)
     x_dims, u_dims = problem.game_cost.x_dims, problem.game_cost.u_dims
     N, n_s, n_c, ids = U.shape[0], x_dims[0], u_dims[0], problem.ids
@@ -174,6 +175,7 @@ def solve_rhc_scenarios(problem, x0, N, radius, xf=None, U0=None, centralized=Fa
     (distributed.py:190-194,215-219: one per receding-horizon round and the closing one), in its format (rhc_log_row);
     i_trial: their trial numbers (a sequence of S, or one value).  The `times` field is wall-clock there and here: each
     agent is given its share of the round's batched solve.  kwargs: n_lqr_iter, tol, t_kill reach every solve.
+    Not built for teams of more than 64 agents (centralized or not): ValueError before any device work.
     Returns a list of S tuples (X_full, U_full, J_full, converged), what solve_rhc returns plus its `converged` flag."""
     import torch
     from .batch import ProblemBatch
@@ -184,6 +186,10 @@ def solve_rhc_scenarios(problem, x0, N, radius, xf=None, U0=None, centralized=Fa
         raise ValueError("Must either specify a convergence cost or distance")
     d = describe(problem)
     k, dt = d["k"], d["dt"]
+    from . import _lib
+    if k > _lib.MAX_AGENTS:
+        raise ValueError(f"solve_rhc_scenarios is not built for teams of more than {_lib.MAX_AGENTS} agents (this one has {k}): "
+                         "solve_scenarios_distributed and solve_distributed serve them, round by round")
     n_x, n_u = problem.dynamics.n_x, problem.dynamics.n_u
     n_s = n_x // k
     x0 = np.asarray(x0, dtype=np.float64).reshape(-1, n_x)

@@ -186,8 +186,12 @@ def perturbed_starts(x0, x_dims, n_samples, n_d=2, var=0.5, seed=None):
 def random_setup_batch(seeds, n_agents, n_states, var, n_d=2, energy=None):
     """(x0, xf) device tensors (S, n_agents * n_states) of the scenarios np.random.seed(s); random_setup(n_agents, n_states,
     is_rotation=False, var=var, n_d=n_d, random=True, energy=energy) for s in range(seeds[0], seeds[0] + S) -- generated on
-    the device, bit for bit what the host loop gives (dpilqr_random_setup).  seeds: (first seed, count) or a range."""
+    the device, bit for bit what the host loop gives (dpilqr_random_setup).  seeds: (first seed, count) or a range.
+    Not built for teams of more than 64 agents (the generator keeps a team's draws in one thread's registers): ValueError."""
     from . import _lib
+    if n_agents > _lib.MAX_AGENTS:
+        raise ValueError(f"random_setup_batch: {n_agents} agents -- the device generator is not built for teams of more than "
+                         f"{_lib.MAX_AGENTS}; draw the scenarios on the host (util.random_setup)")
     from .device import empty, ptr, stream_handle
     seed0, S = (seeds.start, len(seeds)) if isinstance(seeds, range) else (int(seeds[0]), int(seeds[1]))
     if isinstance(seeds, range) and seeds.step != 1:

@@ -336,7 +336,11 @@ int32_t dpilqr_pairwise_graph(int32_t S, int32_t N, int32_t k, int32_t n_s, cons
  *                    U [count][T][kc*n_c] and which slice [first, first+count) of the bucket they are.
  *   dispatch_pack_rows / dispatch_scatter_rows  the multi-GPU form: a rank that solved a slice of every bucket packs one row
  *                    [s*k+i | X columns | U columns] per (scenario, agent) it owns (row_of[S*k], n_rows out; rows == NULL only
- *                    counts); after the path's one all-gather every rank scatters all ranks' rows (index < 0: padding). */
+ *                    counts); after the path's one all-gather every rank scatters all ranks' rows (index < 0: padding).
+ * Teams of 64 < k <= 256 agents: the additive entries dispatch_graph_wide / dispatch_gather_wide / dispatch_stitch_wide
+ * (masks of ceil(k / 64) words) and dpilqr_rollout_wide (the full-team rollout behind J_full), declared with their semantics in
+ * the extension header dpilqr_swarm.h, which is part of this header for every includer (included at its end).  Cluster sizes stay
+ * at most DPILQR_MAX_AGENTS there too.  The entries below answer DPILQR_EINVAL for k > DPILQR_MAX_AGENTS as before. */
 #define DPILQR_MAX_AGENTS 64
 typedef struct dpilqr_bucket_results {
     const double* X[DPILQR_MAX_AGENTS + 1];
@@ -372,6 +376,7 @@ int32_t dpilqr_random_setup(int32_t S, int64_t seed0, int32_t k, int32_t n_s, in
                             double* x0, double* xf, void* stream);
 
 #include "dpilqr_policy.h"
+#include "dpilqr_swarm.h"
 
 #ifdef __cplusplus
 }
