@@ -97,7 +97,11 @@ __device__ R horizon_pass(const dpilqr_batch_desc& D, const ItemParams& P, bool 
     const int mn = m * n;
     const R dtr = (R)D.dt, radius = (R)P.radius, w_prox = (R)D.w_prox, w_ref = (R)D.w_ref;
 
-    R x[NS], xold[NS], u[NC], stK[kMaxStage], std_ = 0.0;
+    // d[t] entries a thread stages per step.  One where n_u <= threads holds by construction: the LDS-staged form (n_x <= 60) and
+    // the matrix-pipe form (forward_on_pipe: n_u <= threads / 2).  The large-cluster form off the pipe is what a launch of few
+    // candidates takes -- ONE alpha is 64 threads -- and config 5 has n_u = 80: up to four (n_u <= 4 * 64 agents' controls).
+    constexpr int kDStage = (KDIRECT && !PIPE) ? 4 : 1;
+    R x[NS], xold[NS], u[NC], stK[kMaxStage], std_[kDStage] = {};
     const int model = active ? P.model[a] : 0;
     const double* xf = P.xf + a * NS;
     const double* Qa = P.Q + a * NS * NS;
@@ -153,7 +157,9 @@ __device__ R horizon_pass(const dpilqr_batch_desc& D, const ItemParams& P, bool 
                     if (e < mn) stK[q] = Kt[e];
                 }
             }
-            if (tid < m) std_ = db[(int64_t)t * m + tid];
+#pragma unroll
+            for (int q = 0; q < kDStage; ++q)
+                if (tid + q * nth < m) std_[q] = db[(int64_t)t * m + tid + q * nth];
         }
         if (active) {
 #pragma unroll
@@ -220,7 +226,9 @@ __device__ R horizon_pass(const dpilqr_batch_desc& D, const ItemParams& P, bool 
                     if (e < mn) sKt[e] = stK[q];
                 }
             }
-            if (tid < m) sdt[tid] = std_;
+#pragma unroll
+            for (int q = 0; q < kDStage; ++q)
+                if (tid + q * nth < m) sdt[tid + q * nth] = std_[q];
         }
         if (active) {
 #pragma unroll

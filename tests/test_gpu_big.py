@@ -250,7 +250,7 @@ def test_large_cluster_passes_vs_oracle(dp, model, k, T):
     K, d = pb.backward_pass(X, U0, to_dev(mu))
     al = orc.alphas()
     Xn, Un, Jn = pb.forward_pass(X, U0, K, d, al)
-    tol_roll = 1e-7 if model == 7 else 1e-11
+    tol_roll = 1.11e-8 if model == 7 else 1e-11      # model 7: ten times the largest per-item bound of tests/test_gpu_forward.py (profiles/forward_checks.txt)
     for i in range(B):
         p = orc.Problem([model] * k, [nd] * k, xf[i], Q, R, Qf, 0.7, 0.1, T)
         Xo, Jo = p.rollout(x0[i], U0[i])

@@ -645,7 +645,9 @@ def test_fuzz_shapes_against_oracle(dp, seed, model, k, T, B, window):
     for i in range(B):
         p = orc.Problem([model] * k, [nd] * k, xf[i], Q, R, Qf, 0.6, 0.1, T)
         Xo, Jo = p.rollout(x0[i], U0[i])
-        tol_roll = 1e-7 if model == 7 else 1e-11   # torque gains of 5e4: last-bit differences of sin / cos / tan grow fast
+        # torque gains of 5e4: last-bit differences of sin / cos / tan grow fast -- ten times the largest per-item bound
+        # tests/test_gpu_forward.py draws for the twelve-state quadcopter from the oracle's own spread (profiles/forward_checks.txt)
+        tol_roll = 1.11e-8 if model == 7 else 1e-11
         assert relerr(X[i].cpu().numpy(), Xo) < tol_roll and abs(float(J[i]) - Jo) <= tol_roll * abs(Jo), i
         Ko, do = p.backward_pass(X[i].cpu().numpy(), U0[i], mu[i])          # same linearisation points as the device
         assert relerr(K[i].cpu().numpy(), Ko) < TOL_PASS and relerr(d[i].cpu().numpy(), do) < TOL_PASS, i
