@@ -112,6 +112,14 @@ SWARM_SIGNATURES = {
     "dpilqr_rollout_wide": (i32, [_DP, vp, vp, vp, vp, vp, vp, vp]),
 }
 
+# ... and of include/dpilqr_order.h: the steps of the solve loop's cost order, stand-alone (csrc/admit_order.hpp)
+ORDER_SIGNATURES = {
+    "dpilqr_cost_keys": (i32, [_DP, vp, vp, vp, vp, vp]),
+    "dpilqr_order_list": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "dpilqr_order_position": (i32, [i32, i32, i32, i32, i32]),
+}
+ORDER_SPREAD, ORDER_GROUPED = 1, 2
+
 MAX_AGENTS = 64          # DPILQR_MAX_AGENTS: agents of a sub-problem (cluster), and of a problem on the one-word entries
 MAX_TEAM = 256           # DPILQR_MAX_TEAM: agents of a problem on the wide entries (include/dpilqr_swarm.h)
 
@@ -138,7 +146,7 @@ def load():
             raise ImportError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                               "(hipcc --offload-arch=gfx950).  dpilqr_amd has no CPU fallback.")
         lib = C.CDLL(str(LIB_PATH))
-        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **SWARM_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **SWARM_SIGNATURES, **ORDER_SIGNATURES}.items():
             fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "dpilqr_hip.h"
+#include "admit_order.hpp"   // SweepDeal, order_position, CostOrder (the kernels live in tu_order.hip)
 #include "launch.hpp"
 #include "models.hpp"    // model_ns / model_nc (host-visible)
 #include "tiles.hpp"     // TileLayout (host-visible)
@@ -318,9 +319,10 @@ int32_t default_solver(dpilqr_solver** out) {
 }
 
 // At the end of an enqueue-only call: bring the double-buffered active list and the counter ring back to the state a
-// call starting at iteration 0 expects (survivors in list 0, their count in counts[0], the other counters zero).
-__global__ void k_normalise_lists(int32_t* lists, int32_t* counts, int window, int it_end) {
-    const int src = it_end & 1, cs = it_end % kCountRing;
+// call starting at iteration 0 expects (survivors in list 0, their count in counts[0], the other counters zero).  src: the list
+// the last line search pushed into (it_end & 1 where no iteration ordered its list; solve_impl keeps track).
+__global__ void k_normalise_lists(int32_t* lists, int32_t* counts, int window, int it_end, int src) {
+    const int cs = it_end % kCountRing;
     __shared__ int n_sh;
     if (threadIdx.x == 0) n_sh = counts[cs];
     __syncthreads();
@@ -480,18 +482,40 @@ int32_t solve_impl(dpilqr_solver* solver, const dpilqr_batch_desc* desc, const R
     // (it pushes only the survivors onto the next list) and k_admit refills their places from the not-yet-started items,
     // so every launch stays at Wn items although the items need very different numbers of iterations.  The active set
     // lives on the device; the host launches Wn-wide grids (surplus workgroups exit at once).
+    // Cost order (admit_order.hpp), for the launches of the fused four-state wavefront sweep above the team tier: survivors and
+    // new items meet in list `surv`, k_order_list scatters them into the other list, the sweep and the line search read that one,
+    // and the line search pushes the next survivors back into `surv`, which is free again by then -- no third list.  An
+    // iteration that does not order its list runs on `surv` itself and pushes into the other list, as ever; `surv` says which
+    // of the two lists holds the survivors when an iteration begins (0 at the start of every call: k_normalise_lists).
+    // The keys lie in the line search's candidate buffer, which is dead between a line search and the next sweep.
+    static const int order_route = route_flag("DPILQR_NO_COST_ORDER") ? (int)kOrderOff : route_int("DPILQR_COST_ORDER", kDefaultCostOrder);
+    const int order = (sizeof(R) == 8 && fused && (order_route == kOrderSpread || order_route == kOrderGrouped)) ? order_route : (int)kOrderOff;
+    int32_t* keys = reinterpret_cast<int32_t*>(ws + W.Xc);
+    int surv = 0;
     size_t n_iterations = 0;
     auto enqueue_iteration = [&](int it, int upper) -> int32_t {
-        int32_t* cur = lists + (size_t)(it & 1) * Wn;
+        int32_t* cur = lists + (size_t)surv * Wn;
+        int32_t* other = lists + (size_t)(surv ^ 1) * Wn;
         int32_t* cur_n = counts + (it % kCountRing);
         int32_t* nxt_n = counts + ((it + 1) % kCountRing);
         int32_t* mail = solver ? solver->dev + kMailWords * (it % kMailRing) : nullptr;
         hipLaunchKernelGGL(k_admit, dim3(1), dim3(256), 0, st, cur, cur_n, nxt_n, admitted_dev, D.B, Wn, mail,
                            (solver && solver->progress) ? 1 : 0, t_admit, S.fault);
         if (solver) HIP_TRY(hipEventRecord(solver->ev[it % kMailRing], st));
-        S.next_items = lists + (size_t)((it + 1) & 1) * Wn;
-        S.next_count = nxt_n;
         int32_t r = DPILQR_OK;
+        const int order_waves = order ? fused_sweep_tier(D, upper) : 0;
+        if (order_waves > 0) {
+            if constexpr (sizeof(R) == 8) {
+                if ((r = launch_cost_keys(D, X, cur, cur_n, upper, kOrderMinLive, keys, st))) return r;
+                if ((r = launch_order_list(cur, other, cur_n, keys, D.T, device_cus(), order_waves, order, kOrderMinLive, st))) return r;
+            }
+            S.next_items = cur;
+            cur = other;
+        } else {
+            S.next_items = other;
+            surv ^= 1;
+        }
+        S.next_count = nxt_n;
         if (fused) {
             if constexpr (sizeof(R) == 8) {
                 prof.begin(1, it, st);
@@ -552,7 +576,7 @@ int32_t solve_impl(dpilqr_solver* solver, const dpilqr_batch_desc* desc, const R
         for (int it = 0; it < n_global_iter; ++it)
             if ((rc = enqueue_iteration(it, Wn))) return rc;
         if (n_global_iter > 0)
-            hipLaunchKernelGGL(k_normalise_lists, dim3(1), dim3(256), 0, st, lists, counts, Wn, n_global_iter);
+            hipLaunchKernelGGL(k_normalise_lists, dim3(1), dim3(256), 0, st, lists, counts, Wn, n_global_iter, surv);
     }
     hipLaunchKernelGGL(k_copy_f64, dim3((D.B + 255) / 256), dim3(256), 0, st, D.B, S.J_last, J);
     if (n_lqr_iter == 0) hipLaunchKernelGGL(k_finish_status, dim3((D.B + 255) / 256), dim3(256), 0, st, D.B, status);
@@ -946,6 +970,32 @@ int64_t dpilqr_solve_iterations_bound(const dpilqr_batch_desc* desc, int32_t win
 int32_t dpilqr_debug_stamps(void* buf) {
     int32_t rc = set_stamp_buffer_riccati(buf);
     return rc ? rc : set_stamp_buffer_forward(buf);
+}
+
+// ---- include/dpilqr_order.h: the two steps of the solve loop's cost order, stand-alone (every list, whatever its length)
+int32_t dpilqr_cost_keys(const dpilqr_batch_desc* desc, const double* X, const int32_t* items, const int32_t* n_items, int32_t* keys,
+                         void* stream) {
+    int32_t rc = check_desc(desc);
+    if (rc) return rc;
+    if (desc->n_s != 4) return fail(DPILQR_EUNSUPPORTED, "cost_keys: n_s=%d, the keys are defined for the four-state family", desc->n_s);
+    if (desc->B == 0) return DPILQR_OK;
+    if (!X || !keys || ((items == nullptr) != (n_items == nullptr))) return fail(DPILQR_EINVAL, "cost_keys: NULL pointer");
+    return launch_cost_keys(*desc, X, items, n_items, desc->B, -1, keys, as_stream(stream));
+}
+
+int32_t dpilqr_order_list(const int32_t* items, const int32_t* n_items, const int32_t* keys, int32_t T, int32_t n_cus, int32_t waves,
+                          int32_t order, int32_t* out, void* stream) {
+    if (!items || !n_items || !keys || !out) return fail(DPILQR_EINVAL, "order_list: NULL pointer");
+    if (T < 1 || n_cus < 1 || (waves != 4 && waves != 8 && waves != 12) || (order != kOrderSpread && order != kOrderGrouped))
+        return fail(DPILQR_EINVAL, "order_list: T=%d n_cus=%d waves=%d order=%d", T, n_cus, waves, order);
+    return launch_order_list(items, out, n_items, keys, T, n_cus, waves, order, -1, as_stream(stream));
+}
+
+int32_t dpilqr_order_position(int32_t rank, int32_t n, int32_t n_cus, int32_t waves, int32_t order) {
+    if (n < 1 || rank < 0 || rank >= n || n_cus < 1 || (waves != 4 && waves != 8 && waves != 12) ||
+        (order != kOrderSpread && order != kOrderGrouped))
+        return fail(DPILQR_EINVAL, "order_position: rank=%d n=%d n_cus=%d waves=%d order=%d", rank, n, n_cus, waves, order);
+    return order_position(rank, SweepDeal(n, n_cus, waves), order);
 }
 
 int32_t dpilqr_profile_enable(dpilqr_solver* solver, int32_t enable) {

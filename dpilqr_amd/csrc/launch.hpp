@@ -7,7 +7,8 @@
 // production), tu_bike.hip (the same for the five-state family, BikeDynamics5D), tu_lsteam.hip (the line search with two
 // wavefronts per item), tu_frontend.hip (the device-side dispatch front / back end), tu_policy.hip (the closed-loop ensemble rollouts),
 // tu_policy_large.hip (the same for n_x > 60), tu_policy_advance.hip (the receding-horizon advance), tu_rollout_wide.hip (the
-// full-team rollout for up to 256 agents) and dpilqr_hip.hip (the C ABI and the solve loop).
+// full-team rollout for up to 256 agents), tu_order.hip (the active list ordered by sweep cost) and dpilqr_hip.hip (the C ABI and
+// the solve loop).
 // No device code crosses a file boundary.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -191,6 +192,17 @@ int32_t launch_riccati_inprod(const dpilqr_batch_desc& D, const double* X, const
 int32_t launch_riccati_bike(const dpilqr_batch_desc& D, const double* X, const double* U, const double* mu, double* K, double* d,
                             int32_t* singular, const int32_t* items, const int32_t* n_items, int grid_items, int gains_by_item,
                             hipStream_t st);
+
+// ---- tu_order.hip: the active list ordered by sweep cost (admit_order.hpp), for the fused four-state wavefront sweep above the
+// team tier.  fused_sweep_tier: wavefronts per workgroup of the sweep launch_riccati_fused makes for grid_items items, 0 for every
+// launch whose list keeps its order.  cost_keys: key[pos] = near-step count of the item at list position pos (list / count null:
+// the batch in index order); order_list: dst = src sorted by key class, heaviest first, dealt by `order` (CostOrder); both leave
+// lists of at most min_live items as they are (order_list copies them).
+int fused_sweep_tier(const dpilqr_batch_desc& D, int grid_items);
+int32_t launch_cost_keys(const dpilqr_batch_desc& D, const double* X, const int32_t* list, const int32_t* count, int grid_items,
+                         int min_live, int32_t* key, hipStream_t st);
+int32_t launch_order_list(const int32_t* src, int32_t* dst, const int32_t* count, const int32_t* key, int T, int cus, int waves,
+                          int order, int min_live, hipStream_t st);
 
 // ---- tu_lsteam.hip: the line search with two wavefronts per item (rollout / costs), for launches of at most 1024 items
 int32_t launch_linesearch_team(const dpilqr_batch_desc& D, double* X, double* U, const double* K, const double* d,
