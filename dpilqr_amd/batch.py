@@ -9,7 +9,7 @@ Python objects on the hot path:
     ilqrSolver._forward_pass   control.py:95-114   -> ProblemBatch.forward_pass
     ilqrSolver.solve           control.py:150-225  -> ProblemBatch.solve
     (no reference counterpart: the feedback policy closed loop)  -> ProblemBatch.policy_rollout, .policy_rollout_large, .policy_rollout_dec
-    (the step between two solves of a receding-horizon loop on a real plant)  -> ProblemBatch.policy_advance, .policy_advance_dec
+    (the step between two solves of a receding-horizon loop on a real plant)  -> ProblemBatch.policy_advance, .policy_advance_large, .policy_advance_dec
 """
 import ctypes as C
 import os
@@ -445,10 +445,17 @@ class ProblemBatch:
                     dist_left=torch.full((S, self.k), float("nan"), dtype=torch.float64, device=x0.device),
                     U_next=zeros((S, self.T, self.n_u)), X_next=zeros((S, self.T + 1, self.n_x)))
 
-    def _advance_shapes(self, who, X, h, state, scen, W, u_lim, n_d, others):
-        """Host-side validation of what policy_advance and policy_advance_dec share (no device access): returns (S, L)."""
+    def _advance_shapes(self, who, X, h, state, scen, W, u_lim, n_d, others, large=False):
+        """Host-side validation of what policy_advance, policy_advance_dec and policy_advance_large share (no device access):
+        returns (S, L).  large: the size test is policy_advance_large's."""
         B, T, k, n, m = self.B, self.T, self.k, self.n_x, self.n_u
-        if n > 60 or k > 20:
+        if large:
+            if n <= 60:
+                raise ValueError(f"{who} serves clusters of 60 < n_x <= 240, this batch has n_x = {n}: use policy_advance")
+            if n > 240 or k > 20 or (self.n_s, self.n_c) not in ((4, 2), (6, 3), (12, 4)):
+                raise ValueError(f"{who} serves clusters of 60 < n_x <= 240 and k <= 20 of the four-, six- and twelve-state families, "
+                                 f"this batch has n_x = {n}, k = {k}, (n_s, n_c) = ({self.n_s}, {self.n_c})")
+        elif n > 60 or k > 20:
             raise ValueError(f"{who} serves clusters up to n_x = 60 and k = 20, this batch has n_x = {n}, k = {k}")
         shape = lambda a: tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)
         for name, a, want in (("X", X, (B, T + 1, n)),) + tuple(others):
@@ -521,6 +528,20 @@ class ProblemBatch:
         K = None if K is None else self._in(K, (B, T, m, n))
         _lib.check(self._lib.dpilqr_policy_advance(self._d, ptr(X), ptr(U), ptr(K), int(h), ptr(scen), S, L, int(n_d), ptr(W),
                                                    ptr(u_lim), *st, stream_handle()))
+        return state
+
+    def policy_advance_large(self, X, U, K, h, state, scen=None, W=None, u_lim=None, n_d=2):
+        """policy_advance for large clusters, 60 < n_x <= 240 with k <= 20 (dpilqr_policy_advance_large): the same arguments, the
+        same state dict (advance_state) and the same semantics.  K[i] (x - X[i]) is formed on the fp64 matrix pipe as
+        policy_rollout_large forms it -- the columns in ascending order, one fused multiply-add per term -- so the executed
+        prefix equals that rollout's bit for bit, and may differ from policy_advance's arithmetic in the last bits."""
+        B, T, n, m = self.B, self.T, self.n_x, self.n_u
+        S, L = self._advance_shapes("policy_advance_large", X, h, state, scen, W, u_lim, n_d,
+                                    (("U", U, (B, T, m)), ("K", K, (B, T, m, n))), large=True)
+        X, U, scen, W, u_lim, st = self._advance_args(X, U, state, scen, W, u_lim, S, L)
+        K = None if K is None else self._in(K, (B, T, m, n))
+        _lib.check(self._lib.dpilqr_policy_advance_large(self._d, ptr(X), ptr(U), ptr(K), int(h), ptr(scen), S, L, int(n_d), ptr(W),
+                                                         ptr(u_lim), *st, stream_handle()))
         return state
 
     def policy_advance_dec(self, X, U_ff, Kc, nbr_bits, h, state, scen=None, W=None, u_lim=None, n_d=2, masks_checked=None):

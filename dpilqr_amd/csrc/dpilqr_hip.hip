@@ -876,6 +876,19 @@ int32_t dpilqr_policy_advance(const dpilqr_batch_desc* desc, const double* X, co
                                            J_exec, min_sep, dist_left, U_next, X_next, as_stream(stream));
 }
 
+int32_t dpilqr_policy_advance_large(const dpilqr_batch_desc* desc, const double* X, const double* U, const double* K, int32_t h,
+                                    const int32_t* scen, int32_t n_scen, int32_t L, int32_t n_d, const double* W, const double* u_lim,
+                                    double* x_cur, int32_t* n_done, double* X_exec, double* U_exec, double* J_exec, double* min_sep,
+                                    double* dist_left, double* U_next, double* X_next, void* stream) {
+    int32_t rc = check_advance_args("policy_advance_large", desc, X, U, K, h, scen, n_scen, L, n_d, W, u_lim, x_cur, n_done,
+                                    X_exec, U_exec, J_exec, min_sep, dist_left, U_next, X_next);
+    if (rc == DPILQR_EUNSUPPORTED && desc->n_s == 5)      // check_desc's refusal of a large five-state cluster, under this entry's name
+        rc = fail(DPILQR_EUNSUPPORTED, "policy_advance_large: the (5, 2) family is served up to n_x = 60, by dpilqr_policy_advance; "
+                                       "served here are the (4, 2), (6, 3) and (12, 4) families with 60 < n_x <= 240, k <= 20");
+    return rc ? rc : launch_policy_advance_large(*desc, X, U, K, h, scen, n_scen, L, n_d, W, u_lim, x_cur, n_done, X_exec, U_exec,
+                                                 J_exec, min_sep, dist_left, U_next, X_next, as_stream(stream));
+}
+
 int32_t dpilqr_policy_advance_dec(const dpilqr_batch_desc* desc, const double* X, const double* U_ff, const double* Kc,
                                   int32_t kc_max, const uint64_t* nbr_bits, int32_t h, const int32_t* scen, int32_t n_scen,
                                   int32_t L, int32_t n_d, const double* W, const double* u_lim, double* x_cur, int32_t* n_done,

@@ -6,7 +6,8 @@
 // tu_team.hip (the fused wavefront sweeps with a helper wavefront per item), tu_inprod.hip (the wavefront sweeps with in-sweep
 // production), tu_bike.hip (the same for the five-state family, BikeDynamics5D), tu_lsteam.hip (the line search with two
 // wavefronts per item), tu_frontend.hip (the device-side dispatch front / back end), tu_policy.hip (the closed-loop ensemble rollouts),
-// tu_policy_large.hip (the same for n_x > 60), tu_policy_advance.hip (the receding-horizon advance), tu_rollout_wide.hip (the
+// tu_policy_large.hip (the same for n_x > 60), tu_policy_advance.hip (the receding-horizon advance),
+// tu_policy_advance_large.hip (the same for n_x > 60), tu_rollout_wide.hip (the
 // full-team rollout for up to 256 agents), tu_order.hip (the active list ordered by sweep cost) and dpilqr_hip.hip (the C ABI and
 // the solve loop).
 // No device code crosses a file boundary.
@@ -243,6 +244,13 @@ int32_t launch_policy_advance(const dpilqr_batch_desc& D, const double* X, const
 int32_t launch_policy_rollout_large(const dpilqr_batch_desc& D, const double* X, const double* U, const double* K, int32_t n_samples,
                                     const double* x0s, const double* W, const double* u_lim, double* Xs, double* Us, double* J,
                                     double* min_sep, double* goal_dist, hipStream_t st);
+
+// ---- tu_policy_advance_large.hip: the receding-horizon advance for 60 < n_x <= 240, dense gains, one workgroup per item, K[i] dx
+// on the matrix pipe (policy_advance_large.hpp); enqueue only
+int32_t launch_policy_advance_large(const dpilqr_batch_desc& D, const double* X, const double* U, const double* K, int32_t h,
+                                    const int32_t* scen, int32_t n_scen, int32_t L, int32_t n_d, const double* W, const double* u_lim,
+                                    double* x_cur, int32_t* n_done, double* X_exec, double* U_exec, double* J_exec, double* min_sep,
+                                    double* dist_left, double* U_next, double* X_next, hipStream_t st);
 
 // ---- tu_rollout_wide.hip: dpilqr_rollout's definition for a full team of up to 256 agents, one workgroup per item
 // (rollout_wide.hpp); X, min_sep, goal_dist may be null; enqueue only

@@ -301,7 +301,7 @@ def solve_rhc_scenarios(problem, x0, N, radius, xf=None, U0=None, centralized=Fa
 
 def solve_rhc_closed_loop(problem, x0, N, radius=None, xf=None, U0=None, centralized=True, feedback=True, W=None, u_lim=None,
                           policy_mu=0.0, n_d=2, step_size=1, dist_converge=None, J_converge=None, max_steps=None, window=None,
-                          **kwargs):
+                          large=False, **kwargs):
     """The receding-horizon loop on a REAL plant, for S scenarios in lock step: plan, execute step_size steps of the plan's
     feedback policy under a disturbance and actuator limits, re-plan from where the plant ended up.  solve_rhc and
     solve_rhc_scenarios keep the reference's ideal plant (xi = X[step_size]); here every round is one batched solve over the
@@ -320,7 +320,11 @@ def solve_rhc_closed_loop(problem, x0, N, radius=None, xf=None, U0=None, central
     Returns a dict: X, U -- lists of S host arrays (n_s + 1, n_x), (n_s, n_u) of the executed lengths --, J (S,) the realised
     cost (stage costs of the executed points plus the terminal cost of the final state), min_sep (S,), goal_dist (S, k),
     converged (S,), n_rounds (S,).
-    Not built: clusters of n_x > 60, fp32, shard=, ignore_ids.  Device problems only."""
+    large=True serves a centralized problem of 60 < n_x <= 240 states and k <= 20 agents (the four-, six- and twelve-state
+    families): every round is ProblemBatch.solve, backward_pass(X, U, policy_mu) with feedback, and one launch of
+    ProblemBatch.policy_advance_large, whose K dx is policy_rollout_large's (one fused multiply-add per term).  A problem of
+    n_x <= 60 takes the route above whatever `large` says.
+    Not built: the distributed loop (centralized=False) for n_x > 60, fp32, shard=, ignore_ids.  Device problems only."""
     import torch
     from .batch import ProblemBatch
     from .device import to_dev
@@ -333,8 +337,15 @@ def solve_rhc_closed_loop(problem, x0, N, radius=None, xf=None, U0=None, central
     if (J_converge is None) == (dist_converge is None):
         raise ValueError("Must either specify a convergence cost or distance")
     n_x, n_u = problem.dynamics.n_x, problem.dynamics.n_u
-    if n_x > 60:
-        raise ValueError(f"solve_rhc_closed_loop serves problems up to n_x = 60, this one has n_x = {n_x}")
+    large = bool(large) and n_x > 60
+    if n_x > 60 and not large:
+        raise ValueError(f"solve_rhc_closed_loop serves problems up to n_x = 60, this one has n_x = {n_x} "
+                         "(large=True serves a centralized problem of up to n_x = 240)")
+    if large and not centralized:
+        raise ValueError("solve_rhc_closed_loop: large=True serves the centralized loop only, the distributed loop for problems of "
+                         f"more than 60 states is not built (this one has n_x = {n_x})")
+    if large and n_x > 240:
+        raise ValueError(f"solve_rhc_closed_loop: large=True serves problems of 60 < n_x <= 240, this one has n_x = {n_x}")
     if not centralized and radius is None:
         raise ValueError("solve_rhc_closed_loop: the distributed solve needs the graph's radius")
     x0 = np.asarray(x0, dtype=np.float64).reshape(-1, n_x)
@@ -354,6 +365,9 @@ def solve_rhc_closed_loop(problem, x0, N, radius=None, xf=None, U0=None, central
     d = describe(problem)
     k, dt = d["k"], d["dt"]
     n_s = n_x // k
+    if large and (k > 20 or (n_s, n_u // k) not in ((4, 2), (6, 3), (12, 4))):
+        raise ValueError(f"solve_rhc_closed_loop: large=True serves teams of k <= 20 agents of the four-, six- and twelve-state "
+                         f"families, this one has k = {k}, (n_s, n_c) = ({n_s}, {n_u // k})")
     if not 1 <= n_d <= n_s:
         raise ValueError(f"solve_rhc_closed_loop: n_d = {n_d}, an agent has {n_s} states")
     solve_kw = solve_kwargs(kwargs, "solve_rhc_closed_loop")
@@ -391,7 +405,8 @@ def solve_rhc_closed_loop(problem, x0, N, radius=None, xf=None, U0=None, central
             pb = batch(ia)
             r = pb.solve(state["x_cur"][ia], state["U_next"][ia], window=window, **solve_kw)
             K = pb.backward_pass(r["X"], r["U"], float(policy_mu))[0] if feedback else None
-            pb.policy_advance(r["X"], r["U"], K, h, state, scen=scen, W=W_d, u_lim=lim_d, n_d=n_d)
+            advance = pb.policy_advance_large if large else pb.policy_advance
+            advance(r["X"], r["U"], K, h, state, scen=scen, W=W_d, u_lim=lim_d, n_d=n_d)
             J[ia] = r["J"]
         else:
             Xin = state["x_cur"][ia][:, None, :] if first else state["X_next"][ia]

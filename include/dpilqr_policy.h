@@ -120,6 +120,25 @@ int32_t dpilqr_policy_advance(const dpilqr_batch_desc* desc, const double* X, co
                               double* x_cur, int32_t* n_done, double* X_exec, double* U_exec, double* J_exec, double* min_sep,
                               double* dist_left, double* U_next, double* X_next, void* stream);
 
+/* The same step for LARGE clusters, 60 < n_x <= 240 with k <= 20: the four-, six- and twelve-state families, models mixed within
+ * a family (the padded HumanDynamics6D among twelve-state agents included).  Arguments, shapes and semantics are
+ * dpilqr_policy_advance's, statement for statement (he, scen, X_exec / U_exec / J_exec with ONE addition per step, min_sep with
+ * the start state when g == 0, dist_left, x_cur, n_done, the shifted U_next / X_next, K NULL: open loop, scenarios not named
+ * untouched, entries of scen out of range skipped), with ONE difference in the arithmetic, the one
+ * dpilqr_policy_rollout_large has against dpilqr_policy_rollout: each entry of K[j][i] (x - X[j][i]) is the sum over columns
+ * 0 .. n_x-1 in that order, ONE FUSED multiply-add per term, starting from zero (the fp64 matrix pipe).  X_exec / U_exec of the
+ * he executed steps equal the prefix of dpilqr_policy_rollout_large's Xs / Us bit for bit (one sample from x_cur[s], W padded
+ * to the horizon).  One workgroup per item; K[i] is read from global memory once per step and never staged
+ * (csrc/policy_advance_large.hpp).
+ * DPILQR_EINVAL: the conditions of dpilqr_policy_advance.  DPILQR_EUNSUPPORTED, before any launch: n_x <= 60 (that is
+ * dpilqr_policy_advance's range), n_x > 240, k > 20, a family other than (4, 2), (6, 3), (12, 4).  B = 0: DPILQR_OK, nothing is
+ * launched.  fp64 only.  Enqueue only, nothing is allocated. */
+int32_t dpilqr_policy_advance_large(const dpilqr_batch_desc* desc, const double* X, const double* U, const double* K, int32_t h,
+                                    const int32_t* scen, int32_t n_scen, int32_t L, int32_t n_d, const double* W,
+                                    const double* u_lim, double* x_cur, int32_t* n_done, double* X_exec, double* U_exec,
+                                    double* J_exec, double* min_sep, double* dist_left, double* U_next, double* X_next,
+                                    void* stream);
+
 /* The same step under a DISTRIBUTED solution's policy: X is the stitched X_dec, the nominal U_ff[B][T][n_u], the gains
  * Kc[B][T][k][n_c][kc_max * n_s] and the masks nbr_bits[B][k] as dpilqr_policy_rollout_dec defines them (members lowest bit
  * first; columns at and past kc_i * n_s are never read; the masks are the caller's contract).  Kc NULL: u = U_ff (open loop:
