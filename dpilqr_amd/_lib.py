@@ -98,6 +98,7 @@ EXT_SIGNATURES = {
     "dpilqr_policy_rollout": (i32, [_DP, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dpilqr_policy_rollout_large": (i32, [_DP, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dpilqr_policy_rollout_dec": (i32, [_DP, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "dpilqr_policy_rollout_dec_team": (i32, [_DP, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dpilqr_dispatch_stitch_policy": (i32, [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dpilqr_policy_advance": (i32, [_DP, vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dpilqr_policy_advance_large": (i32, [_DP, vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -8,7 +8,8 @@ Python objects on the hot path:
     ilqrSolver._backward_pass  control.py:116-148  -> ProblemBatch.make_tiles + backward_pass_tiles
     ilqrSolver._forward_pass   control.py:95-114   -> ProblemBatch.forward_pass
     ilqrSolver.solve           control.py:150-225  -> ProblemBatch.solve
-    (no reference counterpart: the feedback policy closed loop)  -> ProblemBatch.policy_rollout, .policy_rollout_large, .policy_rollout_dec
+    (no reference counterpart: the feedback policy closed loop)  -> ProblemBatch.policy_rollout, .policy_rollout_large, .policy_rollout_dec,
+                                                                    .policy_rollout_dec_team
     (the step between two solves of a receding-horizon loop on a real plant)  -> ProblemBatch.policy_advance, .policy_advance_large, .policy_advance_dec
 """
 import ctypes as C
@@ -426,6 +427,39 @@ class ProblemBatch:
         _lib.check(self._lib.dpilqr_policy_rollout_dec(self._d, ptr(X), ptr(U_ff), ptr(Kc), kc_max, ptr(bits), S, ptr(x0s), ptr(W),
                                                        ptr(u_lim), ptr(out.get("X")), ptr(out.get("U")), ptr(out["J"]),
                                                        ptr(out["min_sep"]), ptr(out["goal_dist"]), stream_handle()))
+        return out
+
+    def _policy_dec_team_shapes(self, X, U_ff, Kc, nbr_bits, x0s, W, u_lim, check_masks=True):
+        """Host-side validation of policy_rollout_dec_team's arguments, as _policy_dec_shapes: (samples per item, kc_max, the
+        masks as a host int64 array -- None with check_masks=False)."""
+        B, T, k, n, m, ns, nc = self.B, self.T, self.k, self.n_x, self.n_u, self.n_s, self.n_c
+        if k > _lib.MAX_AGENTS:
+            raise ValueError(f"policy_rollout_dec_team serves teams of up to {_lib.MAX_AGENTS} agents (a mask is one 64-bit word), "
+                             f"this batch has k = {k}")
+        if ns == 5 and k > 12:
+            raise ValueError(f"policy_rollout_dec_team serves the five-state family up to 12 agents, this batch has k = {k}")
+        sk = tuple(Kc.shape) if isinstance(Kc, torch.Tensor) else np.shape(Kc)
+        if len(sk) != 5 or sk[:4] != (B, T, k, nc) or sk[4] < ns or sk[4] % ns or sk[4] > n:
+            raise ValueError(f"policy_rollout_dec_team: Kc has shape {sk}, expected ({B}, {T}, {k}, {nc}, kc_max * {ns}) with 1 <= kc_max <= {k}")
+        kc_max = sk[4] // ns
+        S = self._policy_common("policy_rollout_dec_team", X, x0s, W, u_lim, (("U_ff", U_ff, (B, T, m)), ("nbr_bits", nbr_bits, (B, k))))
+        if not check_masks:
+            return S, kc_max, None
+        return S, kc_max, self._checked_masks("policy_rollout_dec_team", nbr_bits, kc_max)
+
+    def policy_rollout_dec_team(self, X, U_ff, Kc, nbr_bits, x0s, W=None, u_lim=None, trajectories=False, masks_checked=None):
+        """policy_rollout_dec for a whole team of up to 64 agents at any n_x (dpilqr_policy_rollout_dec_team): the same arguments,
+        the same definition and the same returned dict.  A mask is one 64-bit word (bit 63 a member like any other; int64 masks
+        may be negative).  Where both serve a batch, X, U and goal_dist equal policy_rollout_dec's bit for bit, J and min_sep to
+        rounding (the stage cost is summed agent by agent)."""
+        trusted = masks_checked is not None and masks_checked is nbr_bits and isinstance(nbr_bits, torch.Tensor) and nbr_bits.dtype == torch.int64
+        S, kc_max, bits = self._policy_dec_team_shapes(X, U_ff, Kc, nbr_bits, x0s, W, u_lim, check_masks=not trusted)
+        X, U_ff, x0s, W, u_lim, out = self._policy_stage(S, X, U_ff, x0s, W, u_lim, trajectories)
+        Kc = self._in(Kc, (self.B, self.T, self.k, self.n_c, kc_max * self.n_s))
+        bits = nbr_bits.contiguous() if trusted else torch.from_numpy(bits).to(device())
+        _lib.check(self._lib.dpilqr_policy_rollout_dec_team(self._d, ptr(X), ptr(U_ff), ptr(Kc), kc_max, ptr(bits), S, ptr(x0s), ptr(W),
+                                                            ptr(u_lim), ptr(out.get("X")), ptr(out.get("U")), ptr(out["J"]),
+                                                            ptr(out["min_sep"]), ptr(out["goal_dist"]), stream_handle()))
         return out
 
     # ------------------------------------------------------------------ the receding-horizon advance

@@ -845,6 +845,17 @@ int32_t dpilqr_policy_rollout_dec(const dpilqr_batch_desc* desc, const double* X
                                      as_stream(stream));
 }
 
+int32_t dpilqr_policy_rollout_dec_team(const dpilqr_batch_desc* desc, const double* X, const double* U_ff, const double* Kc, int32_t kc_max,
+                                       const uint64_t* nbr_bits, int32_t n_samples, const double* x0s, const double* W, const double* u_lim,
+                                       double* Xs, double* Us, double* J, double* min_sep, double* goal_dist, void* stream) {
+    const int32_t rc = check_policy_args("policy_rollout_dec_team", desc, n_samples, X, U_ff, Kc, x0s, J, W, u_lim, Xs, Us, min_sep, goal_dist);
+    if (rc) return rc;
+    if (!nbr_bits || reinterpret_cast<uintptr_t>(nbr_bits) % alignof(uint64_t) != 0)
+        return fail(DPILQR_EINVAL, "policy_rollout_dec_team: nbr_bits is a NULL pointer or not aligned to its element type");
+    return launch_policy_rollout_dec_team(*desc, X, U_ff, Kc, kc_max, nbr_bits, n_samples, x0s, W, u_lim, Xs, Us, J, min_sep, goal_dist,
+                                          as_stream(stream));
+}
+
 // the argument checks of the two receding-horizon advances (K, W, u_lim, scen may be null)
 static int32_t check_advance_args(const char* who, const dpilqr_batch_desc* desc, const double* X, const double* U, const double* K,
                                   int32_t h, const int32_t* scen, int32_t n_scen, int32_t L, int32_t n_d, const double* W,

@@ -6,7 +6,8 @@
 // tu_team.hip (the fused wavefront sweeps with a helper wavefront per item), tu_inprod.hip (the wavefront sweeps with in-sweep
 // production), tu_bike.hip (the same for the five-state family, BikeDynamics5D), tu_lsteam.hip (the line search with two
 // wavefronts per item), tu_frontend.hip (the device-side dispatch front / back end), tu_policy.hip (the closed-loop ensemble rollouts),
-// tu_policy_large.hip (the same for n_x > 60), tu_policy_advance.hip (the receding-horizon advance),
+// tu_policy_large.hip (the same for n_x > 60), tu_policy_dec_team.hip (a distributed solution's closed loop for teams of up to
+// 64 agents), tu_policy_advance.hip (the receding-horizon advance),
 // tu_policy_advance_large.hip (the same for n_x > 60), tu_rollout_wide.hip (the
 // full-team rollout for up to 256 agents), tu_order.hip (the active list ordered by sweep cost) and dpilqr_hip.hip (the C ABI and
 // the solve loop).
@@ -232,6 +233,13 @@ int32_t launch_policy_rollout(const dpilqr_batch_desc& D, const double* X, const
 int32_t launch_policy_rollout_dec(const dpilqr_batch_desc& D, const double* X, const double* U_ff, const double* Kc, int32_t kc_max,
                                   const uint64_t* nbr_bits, int32_t n_samples, const double* x0s, const double* W, const double* u_lim,
                                   double* Xs, double* Us, double* J, double* min_sep, double* goal_dist, hipStream_t st);
+
+// ---- tu_policy_dec_team.hip: the same closed loop for a whole team of up to 64 agents at any n_x, a thread per (sample, agent), the
+// gains read straight from global memory (policy_dec_team.hpp); enqueue only
+int32_t launch_policy_rollout_dec_team(const dpilqr_batch_desc& D, const double* X, const double* U_ff, const double* Kc, int32_t kc_max,
+                                       const uint64_t* nbr_bits, int32_t n_samples, const double* x0s, const double* W,
+                                       const double* u_lim, double* Xs, double* Us, double* J, double* min_sep, double* goal_dist,
+                                       hipStream_t st);
 
 // ---- tu_policy_advance.hip: the step between two solves of a receding-horizon loop (policy_advance.hpp): h steps of every running
 // scenario's plan, floor(256 / k) items per workgroup, with the loop's bookkeeping; kc_max == 0: the dense form; enqueue only

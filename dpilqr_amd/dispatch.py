@@ -295,13 +295,16 @@ class DistributedPolicy:
     def rollout(self, x0s, W=None, u_lim=None, trajectories=False):
         """x0s (S, n_samples, n_x) starts per scenario; W (S, n_samples, T, n_x) or None; u_lim (2, n_u) or None.  Returns device
         tensors J, min_sep (S, n_samples), goal_dist (S, n_samples, k) and, with trajectories=True, X, U
-        (ProblemBatch.policy_rollout_dec on the full problem).  The masks are read back and checked by the first call only."""
+        on the full problem: ProblemBatch.policy_rollout_dec where n_x <= 60 and k <= 20, ProblemBatch.policy_rollout_dec_team for
+        every larger team of up to 64 agents.  The masks are read back and checked by the first call only."""
         shape = tuple(x0s.shape) if isinstance(x0s, torch.Tensor) else np.shape(x0s)
         S, n = int(self.X_dec.shape[0]), int(self.X_dec.shape[2])
         if len(shape) != 3 or shape[0] != S or shape[2] != n or shape[1] < 1:
             raise ValueError(f"DistributedPolicy.rollout: x0s has shape {shape}, expected ({S}, n_samples >= 1, {n})")
-        r = self.batch().policy_rollout_dec(self.X_dec, self.U_ff, self.Kc, self.bits, x0s, W=W, u_lim=u_lim,
-                                            trajectories=trajectories, masks_checked=self._masks_checked)
+        pb = self.batch()
+        run = pb.policy_rollout_dec if n <= 60 and self.desc["k"] <= 20 else pb.policy_rollout_dec_team
+        r = run(self.X_dec, self.U_ff, self.Kc, self.bits, x0s, W=W, u_lim=u_lim, trajectories=trajectories,
+                masks_checked=self._masks_checked)
         self._masks_checked = self.bits
         return r
 

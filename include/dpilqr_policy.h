@@ -69,6 +69,31 @@ int32_t dpilqr_policy_rollout_dec(const dpilqr_batch_desc* desc, const double* X
                                   const double* u_lim, double* Xs, double* Us, double* J, double* min_sep, double* goal_dist,
                                   void* stream);
 
+/* The same closed loop for a whole TEAM of up to 64 agents, whatever n_x = k n_s is (64 double integrators: n_x = 256, beyond
+ * every centralised kernel): neighbourhood-only feedback is what a large team can still run.  Arguments, shapes and results are
+ * dpilqr_policy_rollout_dec's and so is the definition, unchanged:
+ *     u_i(t) = clamp( U_ff[b][t][i] + sum ),   sum = columns 0 .. kc_i*n_s-1 of Kc[b][t][i] times (x_{C_i}(t) - X[b][t]_{C_i}),
+ *              ascending, starting from zero, one multiply and one add per term (no contraction)
+ *     x_{t+1} = step(x_t, u_t) [+ W]
+ * with J, min_sep and goal_dist as dpilqr_policy_rollout defines them on the full k-agent problem (all k (k - 1) / 2 pairs,
+ * quirk Q5).  Where both entries serve a shape, Xs, Us and goal_dist agree bit for bit; J and min_sep agree to rounding: a
+ * sample's stage cost is summed agent by agent (each agent's share of the pairs first), in an order that depends on k alone --
+ * no floating-point atomics, the same bits whatever n_samples, the batch or the item's place in it.
+ * A thread per (sample, agent) reads its own compact rows straight from global memory; the K[t] image is never staged
+ * (csrc/policy_dec_team.hpp).  A mask is ONE 64-bit word: bit 63 is a member like any other.
+ * Served: 1 <= k <= 64, every family (models mixed within a family), 1 <= kc_max <= k.  DPILQR_EINVAL: the NULL, alignment and
+ * n_samples < 1 conditions of dpilqr_policy_rollout (nbr_bits as in dpilqr_policy_rollout_dec); (n_s, n_c) not a model family.
+ * DPILQR_EUNSUPPORTED, before any launch: k > 64; more than 12 agents of the five-state family (dpilqr_rollout's limit); kc_max
+ * outside 1 .. k; more than 2^31 - 1 workgroups (one holds floor(256 / k) samples of one item).  B = 0: DPILQR_OK, nothing is
+ * launched.  The masks are the caller's contract as for dpilqr_policy_rollout_dec (own bit, at most kc_max bits among the low
+ * k): a mask that breaks it makes that agent's controls meaningless (members past the kc_max-th are dropped) and no address
+ * depends on it beyond the Kc[b][t] image.  Columns at and past kc_i * n_s are never read.  fp64 only.  Enqueue only, nothing is
+ * allocated. */
+int32_t dpilqr_policy_rollout_dec_team(const dpilqr_batch_desc* desc, const double* X, const double* U_ff, const double* Kc,
+                                       int32_t kc_max, const uint64_t* nbr_bits, int32_t n_samples, const double* x0s,
+                                       const double* W, const double* u_lim, double* Xs, double* Us, double* J, double* min_sep,
+                                       double* goal_dist, void* stream);
+
 /* Gains of the solved sub-problems, per cluster size kc, beside dpilqr_bucket_results (same slices [first, first + count)):
  * K[kc] is [count][T][kc*n_c][kc*n_s], a backward pass at that bucket's (X, U). */
 typedef struct dpilqr_bucket_gains {
