@@ -8,6 +8,9 @@
 //   k_cost_keys   key[pos] = number of steps t in 0..T of the item at list position pos at which the sweep's own criterion
 //                 !(s2 > r * r * (1 + 1e-12)) holds for some pair -- the sweep's expression for s2, evaluated on the X the sweep
 //                 is about to read, so the count is exactly what the sweep will see.
+//                 Optional second output key_dense[pos] = the item's last near step + 1 (0: no near step), at most T + 1: the number
+//                 of steps the sweep runs densely since it walks the steps behind the last near pair per agent
+//                 (riccati_mfma.hpp, "Decoupled prologue"; the terminal step counts, it decides whether the prologue starts).
 //   k_order_list  one workgroup: a counting sort of the list by key class (at most 64 classes, heaviest first; order within a class
 //                 is arbitrary), scattered through order_position into the list the sweep and the line search read.
 // Two orders, both permutations of 0..n-1 produced by the same kernel:
@@ -34,6 +37,9 @@ namespace dpilqr {
 enum CostOrder : int { kOrderOff = 0, kOrderSpread = 1, kOrderGrouped = 2 };
 // The solve loop's order.  A/B route switches (launch.hpp: route_env): DPILQR_NO_COST_ORDER, DPILQR_COST_ORDER=0|1|2.
 constexpr int kDefaultCostOrder = kOrderSpread;
+// The solve loop's key.  A/B route switch DPILQR_COST_KEY=0|1; with the decoupled prologue switched off the count is the key.
+enum CostKey : int { kKeyNearCount = 0, kKeyDenseSteps = 1 };
+constexpr int kDefaultCostKey = kKeyDenseSteps;
 
 constexpr int kOrderMinLive = 1024;   // lists of at most this many items (the team tier, the latency-bound tail) keep their order
 constexpr int kOrderClasses = 64;
@@ -105,7 +111,7 @@ DPILQR_HD inline int order_class(int key, int T) {
 constexpr int kKeyStagedAgents = 5;
 __global__ void __launch_bounds__(256) k_cost_keys(const double* __restrict__ X, const double* __restrict__ radius, int64_t radius_bstride,
                                                    const int32_t* __restrict__ list, const int32_t* __restrict__ count, int B, int T, int k,
-                                                   int min_live, int32_t* __restrict__ key) {
+                                                   int min_live, int32_t* __restrict__ key, int32_t* __restrict__ key_dense) {
     __shared__ double2 sP[4][64 * kKeyStagedAgents];
     const int n = count ? *count : B;
     if (n <= min_live) return;
@@ -119,7 +125,7 @@ __global__ void __launch_bounds__(256) k_cost_keys(const double* __restrict__ X,
     const int nx = 4 * k;
     const double* Xb = X + (int64_t)b * (T + 1) * nx;
     const bool staged = k <= kKeyStagedAgents;
-    int cnt = 0;
+    int cnt = 0, dense = 0;
     for (int t0 = 0; t0 <= T; t0 += 64) {
         const int rows = min(64, T + 1 - t0);
         bool near = false;
@@ -153,9 +159,14 @@ __global__ void __launch_bounds__(256) k_cost_keys(const double* __restrict__ X,
                     near = near || !(s2 > lim);
                 }
         }
-        cnt += __popcll(__builtin_amdgcn_ballot_w64(near));
+        const unsigned long long mask = __builtin_amdgcn_ballot_w64(near);
+        cnt += __popcll(mask);
+        if (mask) dense = t0 + 64 - __clzll(mask);      // the last near step of the chunk, + 1
     }
-    if (lane == 0) key[pos] = cnt;
+    if (lane == 0) {
+        if (key) key[pos] = cnt;
+        if (key_dense) key_dense[pos] = dense;
+    }
 }
 
 // One workgroup.  dst <- src reordered: the counting sort of the n = *count listed items by class, heaviest first, rank r stored at

@@ -489,6 +489,8 @@ int32_t solve_impl(dpilqr_solver* solver, const dpilqr_batch_desc* desc, const R
     // of the two lists holds the survivors when an iteration begins (0 at the start of every call: k_normalise_lists).
     // The keys lie in the line search's candidate buffer, which is dead between a line search and the next sweep.
     static const int order_route = route_flag("DPILQR_NO_COST_ORDER") ? (int)kOrderOff : route_int("DPILQR_COST_ORDER", kDefaultCostOrder);
+    // the key: the sweep's dense steps (last near step + 1) where the decoupled prologue runs, else the near-step count
+    static const bool dense_key = !route_flag("DPILQR_NO_DECOUPLED") && route_int("DPILQR_COST_KEY", kDefaultCostKey) == (int)kKeyDenseSteps;
     const int order = (sizeof(R) == 8 && fused && (order_route == kOrderSpread || order_route == kOrderGrouped)) ? order_route : (int)kOrderOff;
     int32_t* keys = reinterpret_cast<int32_t*>(ws + W.Xc);
     int surv = 0;
@@ -506,7 +508,7 @@ int32_t solve_impl(dpilqr_solver* solver, const dpilqr_batch_desc* desc, const R
         const int order_waves = order ? fused_sweep_tier(D, upper) : 0;
         if (order_waves > 0) {
             if constexpr (sizeof(R) == 8) {
-                if ((r = launch_cost_keys(D, X, cur, cur_n, upper, kOrderMinLive, keys, st))) return r;
+                if ((r = launch_cost_keys(D, X, cur, cur_n, upper, kOrderMinLive, dense_key ? nullptr : keys, dense_key ? keys : nullptr, st))) return r;
                 if ((r = launch_order_list(cur, other, cur_n, keys, D.T, device_cus(), order_waves, order, kOrderMinLive, st))) return r;
             }
             S.next_items = cur;
@@ -1004,7 +1006,9 @@ int32_t dpilqr_cost_keys(const dpilqr_batch_desc* desc, const double* X, const i
     if (desc->n_s != 4) return fail(DPILQR_EUNSUPPORTED, "cost_keys: n_s=%d, the keys are defined for the four-state family", desc->n_s);
     if (desc->B == 0) return DPILQR_OK;
     if (!X || !keys || ((items == nullptr) != (n_items == nullptr))) return fail(DPILQR_EINVAL, "cost_keys: NULL pointer");
-    return launch_cost_keys(*desc, X, items, n_items, desc->B, -1, keys, as_stream(stream));
+    // (test switch, behind DPILQR_DEBUG_ROUTES=1: the kernel's second output, last near step + 1, in place of the count)
+    static const bool second = route_flag("DPILQR_KEYS_DENSE_STEPS");
+    return launch_cost_keys(*desc, X, items, n_items, desc->B, -1, second ? nullptr : keys, second ? keys : nullptr, as_stream(stream));
 }
 
 int32_t dpilqr_order_list(const int32_t* items, const int32_t* n_items, const int32_t* keys, int32_t T, int32_t n_cus, int32_t waves,

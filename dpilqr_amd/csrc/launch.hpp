@@ -198,11 +198,11 @@ int32_t launch_riccati_bike(const dpilqr_batch_desc& D, const double* X, const d
 // ---- tu_order.hip: the active list ordered by sweep cost (admit_order.hpp), for the fused four-state wavefront sweep above the
 // team tier.  fused_sweep_tier: wavefronts per workgroup of the sweep launch_riccati_fused makes for grid_items items, 0 for every
 // launch whose list keeps its order.  cost_keys: key[pos] = near-step count of the item at list position pos (list / count null:
-// the batch in index order); order_list: dst = src sorted by key class, heaviest first, dealt by `order` (CostOrder); both leave
+// the batch in index order), key_dense[pos] = its last near step + 1 (either may be null); order_list: dst = src sorted by key class, heaviest first, dealt by `order` (CostOrder); both leave
 // lists of at most min_live items as they are (order_list copies them).
 int fused_sweep_tier(const dpilqr_batch_desc& D, int grid_items);
 int32_t launch_cost_keys(const dpilqr_batch_desc& D, const double* X, const int32_t* list, const int32_t* count, int grid_items,
-                         int min_live, int32_t* key, hipStream_t st);
+                         int min_live, int32_t* key, int32_t* key_dense, hipStream_t st);
 int32_t launch_order_list(const int32_t* src, int32_t* dst, const int32_t* count, const int32_t* key, int T, int cus, int waves,
                           int order, int min_live, hipStream_t st);
 

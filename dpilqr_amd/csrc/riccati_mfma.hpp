@@ -34,6 +34,9 @@
 //    SIMD, placed deterministically; one wavefront alone gets only half of a SIMD's issue rate.  The live items of a
 //    launch are dealt to the CUs in layers (see the kernel's first lines).
 //
+//  * the DoubleInt4D fused form walks the steps behind the item's last near pair per agent, in registers, before it enters the
+//    dense loop ("Decoupled prologue" in the sweep's body): about half of cfg2's steps.
+//
 //   S1  [T1;T2 | A^T p;B^T p] = [A|B]^T [P|p]  (+ mu B^T on the B rows)   dense: 2x2 tiles x 5 k-steps at cfg2
 //   S2  [T1;T2] [A|B] + l-values -> Q_xx, Q_ux, Q_uu                        dense: 2x2 x 5
 //   S3  LU solve in registers (vector pipe)
@@ -351,6 +354,7 @@ struct FusedArgs {
     dpilqr_batch_desc D;
     const double* X;
     const double* U;
+    int no_decoupled = 0;   // A/B switch DPILQR_NO_DECOUPLED: every step densely (see "Decoupled prologue")
 };
 
 // (The sweep's body, shared by the two kernels below: FUSED 0 tile records, 1 the DoubleInt4D form, 2 the general four-state form.)
@@ -507,38 +511,6 @@ __device__ __forceinline__ void riccati_mfma_sweep(
             return;
         }
     }
-    if constexpr (FUSED) {
-        const ItemParams IP = item_params(F.D, b);
-        constexpr int FKA_ = C::F_KA;
-        const int ag_ = min(lane0 / LPA, KA - 1), sub2_ = min(lane0 - (lane0 / LPA) * LPA, (NM - 1) / RPL);
-#pragma unroll
-        for (int r = 0; r < RPL; ++r) {
-#pragma unroll
-            for (int c = 0; c < NSC; ++c) lvc[r][c] = 0.0;
-            lv_h[r] = -1; lv_neg[r] = false;
-            const int ip = min(RPL * sub2_ + r, NM - 1);
-            if (ip < N) {
-                const int ar = ip >> 2, li = ip & 3;
-                if (ar == ag_) {
-                    const double* Qa = IP.Q + (FGEN ? 16 * ag_ : 0);
-#pragma unroll
-                    for (int c = 0; c < NS; ++c) lvc[r][c] = F.D.w_ref * (Qa[li * 4 + c] + Qa[c * 4 + li]);
-                }
-                if (FKA_ > 1 && li < 2) {
-                    lv_neg[r] = ar != ag_;
-                    lv_h[r] = (ar == ag_) ? (C::oFD - C::oFH) + ag_ * 4 + li * 2
-                                          : ((ar < ag_) ? pair_index(ar, ag_, FKA_) : pair_index(ag_, ar, FKA_)) * 4 + li * 2;
-                }
-            } else {
-                const int a = ip - N;
-                if ((a >> 1) == ag_) {
-                    const double* Ra = IP.R + (FGEN ? 4 * ag_ : 0);
-                    lvc[r][NS] = F.D.w_ref * (Ra[(a & 1) * 2] + Ra[a & 1]);
-                    lvc[r][NS + 1] = F.D.w_ref * (Ra[(a & 1) * 2 + 1] + Ra[2 + (a & 1)]);
-                }
-            }
-        }
-    }
 #include "riccati_mfma_inprod.inc"
     {
     const int lane = lane0;
@@ -633,6 +605,226 @@ __device__ __forceinline__ void riccati_mfma_sweep(
     __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0), expcnt/lgkmcnt untouched
     }
 
+    // ---- Decoupled prologue (the DoubleInt4D form, one wavefront per item).  Walking back from t = T, until the first step at which
+    // some pair is near (f_prox, the sweep's own test, evaluated here) the problem is KA independent per-agent LQR problems:
+    // [A|B], the l-values and P_T are block diagonal, so P, Q_uu, Q_ux and K stay block diagonal and every term the dense step adds
+    // from outside an agent's block is a product with an exact zero.  Such a step is run per agent in registers: lane 8 a + c holds
+    // column c of agent a's block of [P|p] (c = 4: p) and forms column c of T, Q_xx, [Q_ux | Q_u], [K | d] and V with the dense
+    // step's per-output expressions restricted to the block -- S1 / S2 as written below, S3 the 2 x 2 elimination without a row
+    // swap (lu_eliminate<false>), S4 .. S6 each matrix-pipe sum as its ascending chain of fused multiply-adds from +0 over the
+    // agent's two controls.  What crosses lanes goes through 32 doubles per agent in the idle G region; K[t] leaves through a zeroed
+    // [K | d] image in R2 by the dense step's store pattern.  The results are the dense step's up to the sign of zeros.
+    // The step at hand is handed to the dense loop below (P expanded into its LDS image, +0 outside the blocks) at the first near
+    // pair, and at the first doubt: a Q_uu block that is not strictly column dominant (the dense LU would search for pivots, which is
+    // not restated here), a zero pivot, or any non-finite value among the operands that the dense step multiplies by its
+    // structural zeros (0 x Inf would spread NaNs across agents there).  A step is committed -- K[t], d[t] stored, P replaced --
+    // only after the whole wavefront has passed those tests.
+    int t_first = T - 1;
+    if constexpr (FUSED == 1 && !HELP) {
+        if (!F.no_decoupled && !f_prox) {
+            const int lane = lane0;
+            static_assert(32 * KA <= C::szG, "the prologue's exchange area must fit the G region");
+            const ItemParams IP = item_params(F.D, b);
+            const int da = min(lane >> 3, KA - 1), dc = min(lane & 7, 4);     // idle lanes duplicate a working lane
+            const bool dst = dc < 4;                                          // a state column (else: the p column)
+            const int dcol = dst ? 4 * da + dc : N;
+            const double fdt = F.D.dt, wref = F.D.w_ref;
+            double* sX = sG + 32 * da;
+            double Pc[4];
+#pragma unroll
+            for (int l = 0; l < 4; ++l) Pc[l] = sP[(4 * da + l) * LP + dcol];
+            const int cq = dc & 3, cr = dc & 1;
+            const double inf_ = __builtin_inf();
+            double chk0 = fabs(mu) + fabs(fdt);
+#pragma unroll
+            for (int l = 0; l < 4; ++l) chk0 = chk0 + fabs(Pc[l]);
+            if (__builtin_amdgcn_ballot_w64(!(chk0 < inf_)) == 0ull) {
+                DPILQR_LDS_FENCE();
+                for (int e = lane; e < C::szR2; e += 64) sT[e] = 0.0;      // R2 becomes the [K | d] image: zeros off the blocks
+                // the constant l-values, by column, in the idle Q_xx region: w_ref (Q + Q^T)[r][c] at [4 c + r], w_ref (R + R^T)[a][q] at
+                // [16 + 2 q + a]  (lvc's expressions)
+                static_assert(20 <= N * LQ, "the prologue's constants must fit the Q_xx region");
+                if (lane < 16) sQ[lane] = wref * (IP.Q[(lane & 3) * 4 + (lane >> 2)] + IP.Q[(lane >> 2) * 4 + (lane & 3)]);
+                else if (lane < 20) sQ[lane] = wref * (IP.R[(lane & 1) * 2 + ((lane >> 1) & 1)] + IP.R[((lane >> 1) & 1) * 2 + (lane & 1)]);
+                DPILQR_LDS_FENCE();
+                int t = T - 1;
+                for (; t >= 0; --t) {
+                    t_cur = t;
+                    const int lane = phase_lane<REMAT>(lane0);
+#include "riccati_mfma_lane.inc"
+                    fused_step_data(t, nullptr);
+                    if (f_prox) break;                                     // (pf still holds step t's share)
+                    fused_prefetch(t > 0 ? t - 1 : 0);
+                    // S1: column dcol of [A|B]^T [P|p]
+                    double tt[6];
+                    tt[0] = Pc[0];
+                    tt[1] = Pc[1];
+                    tt[2] = fdt * Pc[0] + Pc[2];
+                    tt[3] = fdt * Pc[1] + Pc[3];
+                    tt[4] = fdt * Pc[2];
+                    tt[5] = fdt * Pc[3];
+                    tt[4] = fma(mu, (dst && dc == 2) ? fdt : 0.0, tt[4]);
+                    tt[5] = fma(mu, (dst && dc == 3) ? fdt : 0.0, tt[5]);
+                    if (dc < 2) {
+#pragma unroll
+                        for (int r = 0; r < 6; ++r) sX[2 * r + dc] = tt[r];
+                    }
+                    DPILQR_LDS_FENCE();
+                    // S2: column dc of [T1;T2] A (rows 0..3 Q_xx, rows 4, 5 Q_ux); lanes 2, 3 also column dc - 2 of T2 B (Q_uu).
+                    // The p lane: Q_x, Q_u
+                    double qc[4], gc[2], quu[2];
+                    {
+                        double tu[6], lx[6], lq[4], lr[2];
+                        {
+                            const v2d q0 = *reinterpret_cast<const v2d*>(sQ + 4 * cq), q1 = *reinterpret_cast<const v2d*>(sQ + 4 * cq + 2),
+                                      r0 = *reinterpret_cast<const v2d*>(sQ + 16 + 2 * cr);
+                            lq[0] = q0.x; lq[1] = q0.y; lq[2] = q1.x; lq[3] = q1.y; lr[0] = r0.x; lr[1] = r0.y;
+                        }
+#pragma unroll
+                        for (int r = 0; r < 6; ++r) tu[r] = sX[2 * r + cr];
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) lx[r] = sFL[4 * da + r];
+                        lx[4] = sFL[N + 2 * da]; lx[5] = sFL[N + 2 * da + 1];
+#pragma unroll
+                        for (int r = 0; r < 6; ++r) {
+                            const double o = (dc < 2) ? tt[r] : tu[r] * fdt + tt[r];
+                            const double qv = (r < 4 ? lq[r] : 0.0) + o;
+                            const double v = dst ? qv : lx[r] + tt[r];
+                            if (r < 4) qc[r] = v; else gc[r - 4] = v;
+                        }
+#pragma unroll
+                        for (int a = 0; a < 2; ++a) quu[a] = lr[a] + tt[4 + a] * fdt;
+                    }
+                    DPILQR_LDS_FENCE();
+                    if (dc == 2 || dc == 3) { sX[12 + cr] = quu[0]; sX[14 + cr] = quu[1]; }
+                    DPILQR_LDS_FENCE();
+                    // S3: the agent's 2 x 2 block of Q_uu, eliminated by every lane for its own right-hand side
+                    const double u00 = sX[12], u01 = sX[13], u10 = sX[14], u11 = sX[15];
+                    bool ok;
+                    {
+                        const double cs0 = (0.0 + fabs(u00)) + fabs(u10), cs1 = (0.0 + fabs(u01)) + fabs(u11);
+                        const double dg0 = fabs(u00), dg1 = fabs(u11);
+                        ok = (dg0 * (1.0 - 0x1p-20) > cs0 - dg0) && (dg1 * (1.0 - 0x1p-20) > cs1 - dg1);
+                    }
+                    double inv0 = __builtin_amdgcn_rcp(u00);
+                    inv0 = fma(fma(-u00, inv0, 1.0), inv0, inv0);
+                    inv0 = fma(fma(-u00, inv0, 1.0), inv0, inv0);
+                    const double tm = u10 * (-inv0);
+                    const double w11 = fma(tm, u01, u11), g1 = fma(tm, gc[0], gc[1]);
+                    double inv1 = __builtin_amdgcn_rcp(w11);
+                    inv1 = fma(fma(-w11, inv1, 1.0), inv1, inv1);
+                    inv1 = fma(fma(-w11, inv1, 1.0), inv1, inv1);
+                    double kc[2];
+                    kc[1] = -(g1 * inv1);
+                    kc[0] = -(fma(u01, kc[1], gc[0]) * inv0);
+                    ok = ok && u00 != 0.0 && w11 != 0.0;
+                    // S4: T3^T[.][c] = sum_a Q_uu[a][.] K[a][c]
+                    const double t30 = fma(u10, kc[1], fma(u00, kc[0], 0.0)), t31 = fma(u11, kc[1], fma(u01, kc[0], 0.0));
+                    DPILQR_LDS_FENCE();
+                    if (dst) {
+                        *reinterpret_cast<v2d*>(sX + 6 * dc) = v2d{t30, t31};
+                        *reinterpret_cast<v2d*>(sX + 6 * dc + 2) = v2d{kc[0], kc[1]};
+                        *reinterpret_cast<v2d*>(sX + 6 * dc + 4) = v2d{gc[0], gc[1]};
+                    }
+                    DPILQR_LDS_FENCE();
+                    // S5: V[i][c] = ((Q[i][c] + a1[i][c]) + a2[i][c]) + a2[c][i]
+                    double vc[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const v2d e0 = *reinterpret_cast<const v2d*>(sX + 6 * i), e1 = *reinterpret_cast<const v2d*>(sX + 6 * i + 2),
+                                  e2 = *reinterpret_cast<const v2d*>(sX + 6 * i + 4);
+                        const double a1 = fma(e0.y, kc[1], fma(e0.x, kc[0], 0.0));
+                        const double a2 = fma(e1.y, gc[1], fma(e1.x, gc[0], 0.0));
+                        const double a2t = fma(kc[1], e2.y, fma(kc[0], e2.x, 0.0));
+                        vc[i] = ((qc[i] + a1) + a2) + a2t;
+                    }
+                    DPILQR_LDS_FENCE();
+                    if (dst) {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) sX[4 * i + dc] = vc[i];
+                    }
+                    DPILQR_LDS_FENCE();
+                    // S6: P <- (V + V^T)/2 ; p <- V[:, n]
+                    double pn[4];
+                    {
+                        const v2d w0 = *reinterpret_cast<const v2d*>(sX + 4 * cq), w1 = *reinterpret_cast<const v2d*>(sX + 4 * cq + 2);
+                        pn[0] = dst ? 0.5 * (vc[0] + w0.x) : vc[0];
+                        pn[1] = dst ? 0.5 * (vc[1] + w0.y) : vc[1];
+                        pn[2] = dst ? 0.5 * (vc[2] + w1.x) : vc[2];
+                        pn[3] = dst ? 0.5 * (vc[3] + w1.y) : vc[3];
+                    }
+                    DPILQR_LDS_FENCE();
+                    // every operand the dense step would multiply by a structural zero, and the new [P|p], must be finite
+                    double chk = fabs(u00) + fabs(u01);
+                    chk = chk + fabs(u10); chk = chk + fabs(u11); chk = chk + fabs(w11); chk = chk + fabs(inv0); chk = chk + fabs(inv1);
+                    chk = chk + fabs(gc[0]); chk = chk + fabs(gc[1]); chk = chk + fabs(g1); chk = chk + fabs(kc[0]); chk = chk + fabs(kc[1]);
+                    chk = chk + fabs(t30); chk = chk + fabs(t31);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) chk = chk + fabs(pn[i]);
+                    ok = ok && chk < inf_;
+                    if (__builtin_amdgcn_ballot_w64(!ok) != 0ull) {
+                        fused_prefetch(t);                                 // step t again, densely: its share of (X, U) once more
+                        break;
+                    }
+#pragma unroll
+                    for (int l = 0; l < 4; ++l) Pc[l] = pn[l];
+                    sK[(2 * da) * LK + dcol] = kc[0];
+                    sK[(2 * da + 1) * LK + dcol] = kc[1];
+                    DPILQR_LDS_FENCE();
+                    double* Kt = Kout + (gslot * T + t) * M * N;
+                    double* dt_ = dout + (gslot * T + t) * M;
+#pragma unroll
+                    for (int q = 0; q < K_ROUNDS; ++q) store_v2d_nt(Kt + k_out[q], *reinterpret_cast<const v2d*>(sK + k_in[q]));
+                    store_f64_nt(dt_ + d_idx, sK[d_idx * LK + N]);
+                    DPILQR_LDS_FENCE();
+                }
+                t_first = t;
+                // hand-over: the exchange area and R2 back to zeros, then the blocks of [P|p]
+                for (int e = lane; e < 32 * KA; e += 64) sG[e] = 0.0;
+                if (lane < 20) sQ[lane] = 0.0;
+                for (int e = lane; e < C::szR2; e += 64) sT[e] = 0.0;
+                DPILQR_LDS_FENCE();
+#pragma unroll
+                for (int l = 0; l < 4; ++l) sP[(4 * da + l) * LP + dcol] = Pc[l];
+                DPILQR_LDS_FENCE();
+            }
+        }
+    }
+
+    // (the constant part of the S2 l-values: set up behind the prologue, which has no use for them, so that they are not held across it)
+    if constexpr (FUSED) {
+        const ItemParams IP = item_params(F.D, b);
+        constexpr int FKA_ = C::F_KA;
+        const int ag_ = min(lane0 / LPA, KA - 1), sub2_ = min(lane0 - (lane0 / LPA) * LPA, (NM - 1) / RPL);
+#pragma unroll
+        for (int r = 0; r < RPL; ++r) {
+#pragma unroll
+            for (int c = 0; c < NSC; ++c) lvc[r][c] = 0.0;
+            lv_h[r] = -1; lv_neg[r] = false;
+            const int ip = min(RPL * sub2_ + r, NM - 1);
+            if (ip < N) {
+                const int ar = ip >> 2, li = ip & 3;
+                if (ar == ag_) {
+                    const double* Qa = IP.Q + (FGEN ? 16 * ag_ : 0);
+#pragma unroll
+                    for (int c = 0; c < NS; ++c) lvc[r][c] = F.D.w_ref * (Qa[li * 4 + c] + Qa[c * 4 + li]);
+                }
+                if (FKA_ > 1 && li < 2) {
+                    lv_neg[r] = ar != ag_;
+                    lv_h[r] = (ar == ag_) ? (C::oFD - C::oFH) + ag_ * 4 + li * 2
+                                          : ((ar < ag_) ? pair_index(ar, ag_, FKA_) : pair_index(ag_, ar, FKA_)) * 4 + li * 2;
+                }
+            } else {
+                const int a = ip - N;
+                if ((a >> 1) == ag_) {
+                    const double* Ra = IP.R + (FGEN ? 4 * ag_ : 0);
+                    lvc[r][NS] = F.D.w_ref * (Ra[(a & 1) * 2] + Ra[a & 1]);
+                    lvc[r][NS + 1] = F.D.w_ref * (Ra[(a & 1) * 2 + 1] + Ra[2 + (a & 1)]);
+                }
+            }
+        }
+    }
+
 #ifdef DPILQR_PHASE_STAMPS
     unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ph_t = __builtin_amdgcn_s_memtime();
 #define MPHASE(i) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long now_ = __builtin_amdgcn_s_memtime(); ph[i] += now_ - ph_t; ph_t = now_; }
@@ -641,7 +833,7 @@ __device__ __forceinline__ void riccati_mfma_sweep(
 #else
 #define MPHASE(i)
 #endif
-    for (int t = T - 1; t >= 0; --t) {
+    for (int t = t_first; t >= 0; --t) {
         const int tn = t > 0 ? t - 1 : 0;
         t_cur = t;
         {   // ---- S0, S1

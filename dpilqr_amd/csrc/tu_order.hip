@@ -21,10 +21,10 @@ int fused_sweep_tier(const dpilqr_batch_desc& D, int grid_items) {
 }
 
 int32_t launch_cost_keys(const dpilqr_batch_desc& D, const double* X, const int32_t* list, const int32_t* count, int grid_items,
-                         int min_live, int32_t* key, hipStream_t st) {
+                         int min_live, int32_t* key, int32_t* key_dense, hipStream_t st) {
     if (grid_items <= 0) return DPILQR_OK;
     hipLaunchKernelGGL(k_cost_keys, dim3((grid_items + 3) / 4), dim3(256), 0, st, X, D.radius, D.radius_bstride, list, count, D.B, D.T,
-                       D.k, min_live, key);
+                       D.k, min_live, key, key_dense);
     HIP_TRY(hipGetLastError());
     return DPILQR_OK;
 }

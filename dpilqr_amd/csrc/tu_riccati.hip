@@ -146,12 +146,13 @@ int32_t launch_riccati_fused(const dpilqr_batch_desc& D, const double* X, const 
         if (rc_team != DPILQR_EUNSUPPORTED) return rc_team;
     }
     const int cus = device_cus();
+    static const bool no_dec = route_flag("DPILQR_NO_DECOUPLED");   // A/B switch: every step of the DoubleInt4D form densely
 #define DPILQR_TRY_FUSED(NN, MM)                                                                                   \
     if (n == NN && m == MM)                                                                                        \
         return launch_wave_sweep(k_riccati_mfma<NN, MM, 4, 4, 2, true>, k_riccati_mfma<NN, MM, 8, 4, 2, true>,     \
                                  k_riccati_mfma<NN, MM, 12, 4, 2, true>, sizeof(double) * MfmaCfg<NN, MM, true>::total, \
                                  grid_items, cus, st, D.B, D.T, nullptr, mu, K, d, singular, items, n_items, gains_by_item, \
-                                 cus, FusedArgs{D, X, U});
+                                 cus, FusedArgs{D, X, U, no_dec ? 1 : 0});
     if (fused_wavefront_sweep_applies(D)) {
         DPILQR_WAVE_SIZES(DPILQR_TRY_FUSED)
     }
