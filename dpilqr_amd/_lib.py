@@ -103,6 +103,7 @@ EXT_SIGNATURES = {
     "dpilqr_policy_advance": (i32, [_DP, vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dpilqr_policy_advance_large": (i32, [_DP, vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dpilqr_policy_advance_dec": (i32, [_DP, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "dpilqr_policy_advance_dec_team": (i32, [_DP, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 # ... and of include/dpilqr_swarm.h: teams of 64 < k <= MAX_TEAM agents.  The three dispatch entries take their narrow

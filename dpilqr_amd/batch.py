@@ -10,7 +10,8 @@ Python objects on the hot path:
     ilqrSolver.solve           control.py:150-225  -> ProblemBatch.solve
     (no reference counterpart: the feedback policy closed loop)  -> ProblemBatch.policy_rollout, .policy_rollout_large, .policy_rollout_dec,
                                                                     .policy_rollout_dec_team
-    (the step between two solves of a receding-horizon loop on a real plant)  -> ProblemBatch.policy_advance, .policy_advance_large, .policy_advance_dec
+    (the step between two solves of a receding-horizon loop on a real plant)  -> ProblemBatch.policy_advance, .policy_advance_large, .policy_advance_dec,
+                                                                                 .policy_advance_dec_team
 """
 import ctypes as C
 import os
@@ -479,11 +480,17 @@ class ProblemBatch:
                     dist_left=torch.full((S, self.k), float("nan"), dtype=torch.float64, device=x0.device),
                     U_next=zeros((S, self.T, self.n_u)), X_next=zeros((S, self.T + 1, self.n_x)))
 
-    def _advance_shapes(self, who, X, h, state, scen, W, u_lim, n_d, others, large=False):
-        """Host-side validation of what policy_advance, policy_advance_dec and policy_advance_large share (no device access):
-        returns (S, L).  large: the size test is policy_advance_large's."""
+    def _advance_shapes(self, who, X, h, state, scen, W, u_lim, n_d, others, large=False, team=False):
+        """Host-side validation of what policy_advance, policy_advance_dec, policy_advance_large and policy_advance_dec_team
+        share (no device access): returns (S, L).  large: the size test is policy_advance_large's; team: the team advance's."""
         B, T, k, n, m = self.B, self.T, self.k, self.n_x, self.n_u
-        if large:
+        if team:
+            if k > _lib.MAX_AGENTS:
+                raise ValueError(f"{who} serves teams of up to {_lib.MAX_AGENTS} agents (a mask is one 64-bit word), "
+                                 f"this batch has k = {k}")
+            if self.n_s == 5 and k > 12:
+                raise ValueError(f"{who} serves the five-state family up to 12 agents, this batch has k = {k}")
+        elif large:
             if n <= 60:
                 raise ValueError(f"{who} serves clusters of 60 < n_x <= 240, this batch has n_x = {n}: use policy_advance")
             if n > 240 or k > 20 or (self.n_s, self.n_c) not in ((4, 2), (6, 3), (12, 4)):
@@ -582,8 +589,18 @@ class ProblemBatch:
         """policy_advance under a distributed solution's policy (dpilqr_policy_advance_dec): X the stitched trajectory, U_ff,
         Kc (B,T,k,n_c,kc_max*n_s) and nbr_bits (B,k) as policy_rollout_dec takes them, masks_checked included.  Kc None: the
         plan U_ff (then U_dec) is executed open loop and the masks are not read."""
+        return self._policy_advance_dec("policy_advance_dec", False, X, U_ff, Kc, nbr_bits, h, state, scen, W, u_lim, n_d, masks_checked)
+
+    def policy_advance_dec_team(self, X, U_ff, Kc, nbr_bits, h, state, scen=None, W=None, u_lim=None, n_d=2, masks_checked=None):
+        """policy_advance_dec for a whole team of up to 64 agents at any n_x (dpilqr_policy_advance_dec_team): the same
+        arguments, the same state dict (advance_state) and the same semantics, with policy_rollout_dec_team's arithmetic.  A mask
+        is one 64-bit word (bit 63 a member like any other; int64 masks may be negative).  The executed prefix equals
+        policy_rollout_dec_team's bit for bit; where policy_advance_dec serves the batch too, everything but J_exec and min_sep
+        equals its results bit for bit, those two to rounding (the stage cost is summed agent by agent)."""
+        return self._policy_advance_dec("policy_advance_dec_team", True, X, U_ff, Kc, nbr_bits, h, state, scen, W, u_lim, n_d, masks_checked)
+
+    def _policy_advance_dec(self, who, team, X, U_ff, Kc, nbr_bits, h, state, scen, W, u_lim, n_d, masks_checked):
         B, T, k, n, m, ns, nc = self.B, self.T, self.k, self.n_x, self.n_u, self.n_s, self.n_c
-        who = "policy_advance_dec"
         kc_max = 1
         if Kc is not None:
             sk = tuple(Kc.shape) if isinstance(Kc, torch.Tensor) else np.shape(Kc)
@@ -591,7 +608,7 @@ class ProblemBatch:
                 raise ValueError(f"{who}: Kc has shape {sk}, expected ({B}, {T}, {k}, {nc}, kc_max * {ns}) with 1 <= kc_max <= {k}")
             kc_max = sk[4] // ns
         others = (("U_ff", U_ff, (B, T, m)),) + ((("nbr_bits", nbr_bits, (B, k)),) if Kc is not None else ())
-        S, L = self._advance_shapes(who, X, h, state, scen, W, u_lim, n_d, others)
+        S, L = self._advance_shapes(who, X, h, state, scen, W, u_lim, n_d, others, team=team)
         bits = None
         if Kc is not None:
             if nbr_bits is None:
@@ -600,8 +617,9 @@ class ProblemBatch:
             bits = nbr_bits.contiguous() if trusted else torch.from_numpy(self._checked_masks(who, nbr_bits, kc_max)).to(device())
             Kc = self._in(Kc, (B, T, k, nc, kc_max * ns))
         X, U_ff, scen, W, u_lim, st = self._advance_args(X, U_ff, state, scen, W, u_lim, S, L)
-        _lib.check(self._lib.dpilqr_policy_advance_dec(self._d, ptr(X), ptr(U_ff), ptr(Kc), kc_max, ptr(bits), int(h), ptr(scen), S, L,
-                                                       int(n_d), ptr(W), ptr(u_lim), *st, stream_handle()))
+        entry = self._lib.dpilqr_policy_advance_dec_team if team else self._lib.dpilqr_policy_advance_dec
+        _lib.check(entry(self._d, ptr(X), ptr(U_ff), ptr(Kc), kc_max, ptr(bits), int(h), ptr(scen), S, L, int(n_d), ptr(W), ptr(u_lim),
+                         *st, stream_handle()))
         return state
 
     def cost(self, x, u, terminal=False):

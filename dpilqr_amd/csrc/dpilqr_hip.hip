@@ -918,6 +918,20 @@ int32_t dpilqr_policy_advance_dec(const dpilqr_batch_desc* desc, const double* X
                                  J_exec, min_sep, dist_left, U_next, X_next, as_stream(stream));
 }
 
+int32_t dpilqr_policy_advance_dec_team(const dpilqr_batch_desc* desc, const double* X, const double* U_ff, const double* Kc,
+                                       int32_t kc_max, const uint64_t* nbr_bits, int32_t h, const int32_t* scen, int32_t n_scen,
+                                       int32_t L, int32_t n_d, const double* W, const double* u_lim, double* x_cur, int32_t* n_done,
+                                       double* X_exec, double* U_exec, double* J_exec, double* min_sep, double* dist_left,
+                                       double* U_next, double* X_next, void* stream) {
+    const int32_t rc = check_advance_args("policy_advance_dec_team", desc, X, U_ff, Kc, h, scen, n_scen, L, n_d, W, u_lim, x_cur, n_done,
+                                          X_exec, U_exec, J_exec, min_sep, dist_left, U_next, X_next);
+    if (rc) return rc;
+    if ((Kc && !nbr_bits) || reinterpret_cast<uintptr_t>(nbr_bits) % alignof(uint64_t) != 0)
+        return fail(DPILQR_EINVAL, "policy_advance_dec_team: nbr_bits is a NULL pointer or not aligned to its element type");
+    return launch_policy_advance_dec_team(*desc, X, U_ff, Kc, kc_max, nbr_bits, h, scen, n_scen, L, n_d, W, u_lim, x_cur, n_done, X_exec,
+                                          U_exec, J_exec, min_sep, dist_left, U_next, X_next, as_stream(stream));
+}
+
 int32_t dpilqr_alphas(double* alphas_host) {
     if (!alphas_host) return fail(DPILQR_EINVAL, "alphas: NULL pointer");
     alpha_table(alphas_host);

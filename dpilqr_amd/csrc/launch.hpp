@@ -248,6 +248,14 @@ int32_t launch_policy_advance(const dpilqr_batch_desc& D, const double* X, const
                               const double* W, const double* u_lim, double* x_cur, int32_t* n_done, double* X_exec, double* U_exec,
                               double* J_exec, double* min_sep, double* dist_left, double* U_next, double* X_next, hipStream_t st);
 
+// ---- tu_policy_advance_dec_team.hip: the same step under a distributed solution's policy for a whole team of up to 64 agents at
+// any n_x, a thread per (item, agent), the team rollout's arithmetic (policy_advance_dec_team.hpp); Kc null: open loop; enqueue only
+int32_t launch_policy_advance_dec_team(const dpilqr_batch_desc& D, const double* X, const double* U_ff, const double* Kc, int32_t kc_max,
+                                       const uint64_t* nbr_bits, int32_t h, const int32_t* scen, int32_t n_scen, int32_t L, int32_t n_d,
+                                       const double* W, const double* u_lim, double* x_cur, int32_t* n_done, double* X_exec,
+                                       double* U_exec, double* J_exec, double* min_sep, double* dist_left, double* U_next,
+                                       double* X_next, hipStream_t st);
+
 // ---- tu_policy_large.hip: the same rollout for 60 < n_x <= 240, K[t] dx on the matrix pipe (policy_large.hpp); enqueue only
 int32_t launch_policy_rollout_large(const dpilqr_batch_desc& D, const double* X, const double* U, const double* K, int32_t n_samples,
                                     const double* x0s, const double* W, const double* u_lim, double* Xs, double* Us, double* J,

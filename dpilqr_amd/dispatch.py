@@ -308,11 +308,16 @@ class DistributedPolicy:
         self._masks_checked = self.bits
         return r
 
-    def advance(self, h, state, scen=None, W=None, u_lim=None, n_d=2):
+    def advance(self, h, state, scen=None, W=None, u_lim=None, n_d=2, team=False):
         """Execute h steps of every scenario's policy on the plant state kept in `state` and shift the plan
-        (ProblemBatch.policy_advance_dec on the full problem): the step between two solves of a receding-horizon loop."""
-        r = self.batch().policy_advance_dec(self.X_dec, self.U_ff, self.Kc, self.bits, h, state, scen=scen, W=W, u_lim=u_lim, n_d=n_d,
-                                            masks_checked=self._masks_checked)
+        (ProblemBatch.policy_advance_dec on the full problem): the step between two solves of a receding-horizon loop.
+        team=True: a team of n_x > 60 or k > 20 (up to 64 agents) goes through ProblemBatch.policy_advance_dec_team, every
+        smaller one through policy_advance_dec as without it."""
+        pb = self.batch()
+        n = int(self.X_dec.shape[2])
+        run = pb.policy_advance_dec_team if team and (n > 60 or self.desc["k"] > 20) else pb.policy_advance_dec
+        r = run(self.X_dec, self.U_ff, self.Kc, self.bits, h, state, scen=scen, W=W, u_lim=u_lim, n_d=n_d,
+                masks_checked=self._masks_checked)
         self._masks_checked = self.bits
         return r
 

@@ -301,7 +301,7 @@ def solve_rhc_scenarios(problem, x0, N, radius, xf=None, U0=None, centralized=Fa
 
 def solve_rhc_closed_loop(problem, x0, N, radius=None, xf=None, U0=None, centralized=True, feedback=True, W=None, u_lim=None,
                           policy_mu=0.0, n_d=2, step_size=1, dist_converge=None, J_converge=None, max_steps=None, window=None,
-                          large=False, **kwargs):
+                          large=False, team=False, **kwargs):
     """The receding-horizon loop on a REAL plant, for S scenarios in lock step: plan, execute step_size steps of the plan's
     feedback policy under a disturbance and actuator limits, re-plan from where the plant ended up.  solve_rhc and
     solve_rhc_scenarios keep the reference's ideal plant (xi = X[step_size]); here every round is one batched solve over the
@@ -324,7 +324,12 @@ def solve_rhc_closed_loop(problem, x0, N, radius=None, xf=None, U0=None, central
     families): every round is ProblemBatch.solve, backward_pass(X, U, policy_mu) with feedback, and one launch of
     ProblemBatch.policy_advance_large, whose K dx is policy_rollout_large's (one fused multiply-add per term).  A problem of
     n_x <= 60 takes the route above whatever `large` says.
-    Not built: the distributed loop (centralized=False) for n_x > 60, fp32, shard=, ignore_ids.  Device problems only."""
+    team=True serves the DISTRIBUTED loop (centralized=False) of any lowerable team of up to 64 agents, whatever n_x is (64
+    double integrators: n_x = 256): every round is solve_scenarios_distributed(policy=feedback, ...) and one launch of
+    ProblemBatch.policy_advance_dec_team -- DistributedPolicy.advance(..., team=True) with feedback, the stitched plan open loop
+    without --, whose arithmetic is policy_rollout_dec_team's.  A problem of n_x <= 60 and k <= 20 takes the route above
+    whatever `team` says.  It is opt-in: without it a larger distributed problem is refused as before.
+    Not built: teams of more than 64 agents, fp32, shard=, ignore_ids.  Device problems only."""
     import torch
     from .batch import ProblemBatch
     from .device import to_dev
@@ -338,9 +343,14 @@ def solve_rhc_closed_loop(problem, x0, N, radius=None, xf=None, U0=None, central
         raise ValueError("Must either specify a convergence cost or distance")
     n_x, n_u = problem.dynamics.n_x, problem.dynamics.n_u
     large = bool(large) and n_x > 60
-    if n_x > 60 and not large:
+    if team and centralized:
+        raise ValueError("solve_rhc_closed_loop: team=True is the distributed loop (centralized=False); a centralized problem of "
+                         "60 < n_x <= 240 is served by large=True")
+    team = bool(team) and not large and n_x > 60      # (more than 20 agents have more than 60 states: an agent has at least three)
+    if n_x > 60 and not large and not team:
         raise ValueError(f"solve_rhc_closed_loop serves problems up to n_x = 60, this one has n_x = {n_x} "
-                         "(large=True serves a centralized problem of up to n_x = 240)")
+                         "(large=True serves a centralized problem of up to n_x = 240, team=True the distributed loop of a team "
+                         "of up to 64 agents)")
     if large and not centralized:
         raise ValueError("solve_rhc_closed_loop: large=True serves the centralized loop only, the distributed loop for problems of "
                          f"more than 60 states is not built (this one has n_x = {n_x})")
@@ -365,6 +375,12 @@ def solve_rhc_closed_loop(problem, x0, N, radius=None, xf=None, U0=None, central
     d = describe(problem)
     k, dt = d["k"], d["dt"]
     n_s = n_x // k
+    if team:
+        from . import _lib
+        if k > _lib.MAX_AGENTS:
+            raise ValueError(f"solve_rhc_closed_loop is not built for teams of more than {_lib.MAX_AGENTS} agents (this one has {k})")
+        if n_s == 5 and k > 12:
+            raise ValueError(f"solve_rhc_closed_loop: team=True serves the five-state family up to 12 agents, this one has k = {k}")
     if large and (k > 20 or (n_s, n_u // k) not in ((4, 2), (6, 3), (12, 4))):
         raise ValueError(f"solve_rhc_closed_loop: large=True serves teams of k <= 20 agents of the four-, six- and twelve-state "
                          f"families, this one has k = {k}, (n_s, n_c) = ({n_s}, {n_u // k})")
@@ -414,9 +430,11 @@ def solve_rhc_closed_loop(problem, x0, N, radius=None, xf=None, U0=None, central
                                                            device_out=True, desc=d, policy=bool(feedback), policy_mu=float(policy_mu),
                                                            **solve_kw)
             if feedback:
-                info["policy"].advance(h, state, scen=scen, W=W_d, u_lim=lim_d, n_d=n_d)
+                info["policy"].advance(h, state, scen=scen, W=W_d, u_lim=lim_d, n_d=n_d, team=team)
             else:
-                batch(ia).policy_advance_dec(Xa, Ua, None, None, h, state, scen=scen, W=W_d, u_lim=lim_d, n_d=n_d)
+                pb = batch(ia)
+                advance = pb.policy_advance_dec_team if team else pb.policy_advance_dec
+                advance(Xa, Ua, None, None, h, state, scen=scen, W=W_d, u_lim=lim_d, n_d=n_d)
             J[ia] = Ja
         first = False
         n_rounds[active] += 1

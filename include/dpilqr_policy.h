@@ -174,4 +174,35 @@ int32_t dpilqr_policy_advance_dec(const dpilqr_batch_desc* desc, const double* X
                                   double* X_exec, double* U_exec, double* J_exec, double* min_sep, double* dist_left,
                                   double* U_next, double* X_next, void* stream);
 
+/* The same step for a whole TEAM of up to 64 agents, whatever n_x = k n_s is: the receding-horizon advance of the teams
+ * dpilqr_policy_rollout_dec_team serves.  Arguments and shapes are dpilqr_policy_advance_dec's, and the semantics are
+ * dpilqr_policy_advance's, statement for statement: he = min(h, L - n_done[s]); scen maps items to scenarios, an entry out of
+ * range is skipped, scenarios not named are untouched; X_exec, U_exec and J_exec are appended at the scenario's own offset, with
+ * ONE addition to J_exec per executed step, in time order; the start state opens min_sep when n_done[s] == 0; dist_left over n_d
+ * coordinates; x_cur and n_done updated; the shifted U_next / X_next (which must not alias the plan); Kc NULL: U_ff is executed
+ * open loop and the masks are not read (nbr_bits may then be NULL).  The arithmetic is dpilqr_policy_rollout_dec_team's:
+ *     u_i = clamp( U_ff[j][t][i] + sum ),   sum = columns 0 .. kc_i*n_s-1 of Kc[j][t][i] times (x_{C_i} - X[j][t]_{C_i}),
+ *           ascending, starting from zero, one multiply and one add per term; the members of the 64-bit mask lowest bit first
+ *     x = step(x, u) [+ W[s][g+t]]                          the model step is taken, then W is added
+ *     the stage cost of a step: the k per-agent terms added in agent order, each w_prox times that agent's pair costs in
+ *     ascending partner offset plus w_ref times its reference cost
+ * so X_exec / U_exec of the he executed steps equal the prefix of dpilqr_policy_rollout_dec_team's Xs / Us bit for bit (one
+ * sample from x_cur[s], W padded to the horizon).  Where dpilqr_policy_advance_dec also serves the shape, X_exec, U_exec, x_cur,
+ * n_done, dist_left, U_next and X_next agree with it bit for bit; J_exec and min_sep agree to rounding (the relation the two
+ * rollouts have).  No floating-point atomics: the same bits whatever the batch or the item's place in it.  One workgroup holds
+ * floor(256 / k) ITEMS, a thread per (item, agent) reads its own compact rows straight from global memory
+ * (csrc/policy_advance_dec_team.hpp).
+ * Served: 1 <= k <= 64, every family (models mixed within a family), 1 <= kc_max <= k.  DPILQR_EINVAL: the conditions of
+ * dpilqr_policy_advance; nbr_bits NULL while Kc is given, or misaligned; (n_s, n_c) not a model family.  DPILQR_EUNSUPPORTED,
+ * before any launch: k > 64; more than 12 agents of the five-state family (dpilqr_rollout's limit); kc_max outside 1 .. k; more
+ * than 2^31 - 1 workgroups.  B = 0: DPILQR_OK, nothing is launched.  The masks are the caller's contract as for
+ * dpilqr_policy_rollout_dec (own bit, at most kc_max bits among the low k): a mask that breaks it makes that agent's controls
+ * meaningless (members past the kc_max-th are dropped) and no address depends on it beyond the item's own Kc[j][t] image.
+ * Columns at and past kc_i * n_s are never read.  fp64 only.  Enqueue only, nothing is allocated. */
+int32_t dpilqr_policy_advance_dec_team(const dpilqr_batch_desc* desc, const double* X, const double* U_ff, const double* Kc,
+                                       int32_t kc_max, const uint64_t* nbr_bits, int32_t h, const int32_t* scen, int32_t n_scen,
+                                       int32_t L, int32_t n_d, const double* W, const double* u_lim, double* x_cur,
+                                       int32_t* n_done, double* X_exec, double* U_exec, double* J_exec, double* min_sep,
+                                       double* dist_left, double* U_next, double* X_next, void* stream);
+
 #endif /* DPILQR_POLICY_H */
