@@ -94,17 +94,14 @@ SIGNATURES = {
 }
 
 # additive entry points of the extension headers dpilqr_hip.h includes (include/dpilqr_policy.h); bound by load() like the rest
-EXT_SIGNATURES = {
-    "dpilqr_policy_rollout": (i32, [_DP, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "dpilqr_policy_rollout_large": (i32, [_DP, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "dpilqr_policy_rollout_dec": (i32, [_DP, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "dpilqr_policy_rollout_dec_team": (i32, [_DP, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "dpilqr_dispatch_stitch_policy": (i32, [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "dpilqr_policy_advance": (i32, [_DP, vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "dpilqr_policy_advance_large": (i32, [_DP, vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "dpilqr_policy_advance_dec": (i32, [_DP, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "dpilqr_policy_advance_dec_team": (i32, [_DP, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-}
+# The eight closed-loop entries: a kind's arguments -- desc, the plan X, U, K | the rest, the stream last -- and, for the two
+# neighbourhood forms of each kind (_dec, _dec_team), (kc_max, nbr_bits) behind the plan
+_PLAN = [_DP, vp, vp, vp]
+_CLOSED_LOOP_ARGS = {"rollout": [i32] + [vp] * 9,                        # n_samples, x0s, W, u_lim, Xs, Us, J, min_sep, goal_dist, stream
+                     "advance": [i32, vp, i32, i32, i32] + [vp] * 12}    # h, scen, n_scen, L, n_d, W, u_lim, the nine state fields, stream
+EXT_SIGNATURES = {f"dpilqr_policy_{kind}{form}": (i32, _PLAN + ([i32, vp] if "_dec" in form else []) + rest)
+                  for kind, rest in _CLOSED_LOOP_ARGS.items() for form in ("", "_large", "_dec", "_dec_team")}
+EXT_SIGNATURES["dpilqr_dispatch_stitch_policy"] = (i32, [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
 
 # ... and of include/dpilqr_swarm.h: teams of 64 < k <= MAX_TEAM agents.  The three dispatch entries take their narrow
 # counterparts' arguments plus n_words (before the stream)

@@ -24,6 +24,49 @@ from .device import device, empty, ptr, stream_handle, to_dev, zeros
 
 MODEL_DIMS = {0: (4, 2), 1: (6, 3), 2: (3, 2), 3: (4, 2), 4: (6, 3), 5: (6, 3), 6: (6, 3), 7: (12, 4), 8: (12, 4), 10: (5, 2)}
 
+# The closed-loop routes: which (k, n_s, n_c) the closed-loop entry points serve, and the words they refuse the rest with.  This
+# is the ONE place the limits are written on the Python side -- the validators below, DistributedPolicy (dispatch.py) and
+# solve_rhc_closed_loop (distributed.py) ask route_refusal / route_serves -- as the closed-loop section of csrc/launch.hpp is on
+# the C side; tests/test_closed_loop_routes_host.py holds the two to each other.  A route serves above_nx < n_x <= max_nx with
+# k <= max_k agents (k <= max_k_of_ns[n_s] for the state sizes named there) of `families` (None: every family).
+_SMALL = dict(above_nx=0, max_nx=60, max_k=20, families=None, max_k_of_ns={}, text=dict(
+    beyond="{who} serves clusters up to n_x = {max_nx} and k = {max_k}, this batch has n_x = {n}, k = {k}"))
+ROUTES = {
+    "small": _SMALL,      # policy_rollout, policy_rollout_dec, policy_advance, policy_advance_dec
+    "large": dict(above_nx=_SMALL["max_nx"], max_nx=240, max_k=_SMALL["max_k"], families=((4, 2), (6, 3), (12, 4)), max_k_of_ns={}, text=dict(
+        below="{who} serves clusters of {above_nx} < n_x <= {max_nx}, this batch has n_x = {n}: use {use}",
+        beyond="{who} serves clusters of {above_nx} < n_x <= {max_nx} and k <= {max_k} of the four-, six- and twelve-state families, "
+               "this batch has n_x = {n}, k = {k}, (n_s, n_c) = ({n_s}, {n_c})")),      # policy_rollout_large, policy_advance_large
+    "team": dict(above_nx=0, max_nx=float("inf"), max_k=_lib.MAX_AGENTS, families=None, max_k_of_ns={5: 12}, text=dict(
+        beyond="{who} serves teams of up to {max_k} agents (a mask is one 64-bit word), this batch has k = {k}",
+        family="{who} serves the five-state family up to {max_k_of_ns[5]} agents, this batch has k = {k}")),      # the two _dec_team
+}
+# an entry whose words differ from its route's
+ROUTE_TEXT_OF = {"policy_rollout": dict(beyond="{who} serves clusters up to n_x = {max_nx}, this batch has n_x = {n}")}
+
+
+def route_refusal(route, k, n_s, n_c):
+    """None where `route` serves k agents of the (n_s, n_c) family, else the limit it misses: a key of ROUTES[route]['text']."""
+    r, n = ROUTES[route], k * n_s
+    if n <= r["above_nx"]:
+        return "below"
+    if n > r["max_nx"] or k > r["max_k"] or (r["families"] is not None and (n_s, n_c) not in r["families"]):
+        return "beyond"
+    return "family" if k > r["max_k_of_ns"].get(n_s, k) else None
+
+
+def route_serves(route, k, n_s, n_c):
+    return route_refusal(route, k, n_s, n_c) is None
+
+
+def _shape(a):
+    return tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)
+
+
+def _masks_trusted(masks_checked, nbr_bits):
+    """masks_checked is the very int64 device tensor given as nbr_bits: an earlier call has read it back and checked it."""
+    return masks_checked is not None and masks_checked is nbr_bits and isinstance(nbr_bits, torch.Tensor) and nbr_bits.dtype == torch.int64
+
 
 def _shared_or_batched(a, B, per_item_shape, dtype):
     """Returns (device tensor, batch stride in elements): stride 0 when one copy serves the batch."""
@@ -213,7 +256,7 @@ class ProblemBatch:
     @property
     def is_large(self):
         """n_x > 60: the large-cluster kernels serve this batch (the fused sweep above, policy_rollout_large below)."""
-        return self.n_x > 60
+        return self.n_x > ROUTES["small"]["max_nx"]
 
     def _in(self, a, shape, dtype=torch.float64):
         t = to_dev(a, dtype)
@@ -300,46 +343,95 @@ class ProblemBatch:
         _lib.check(fn(self._d, ptr(X), ptr(U), ptr(K), ptr(d), ptr(al), A, ptr(Xn), ptr(Un), ptr(Jn), stream_handle()))
         return Xn, Un, Jn
 
-    def _policy_common(self, who, X, x0s, W, u_lim, others):
-        """Host-side validation of what policy_rollout and policy_rollout_dec share (no device access): X, x0s, W, u_lim and
-        `others` -- (name, array, shape) of the caller's further arrays --; `who` is the caller's name in the messages.  Returns
-        the number of samples per item."""
-        B, T, n, m = self.B, self.T, self.n_x, self.n_u
-        shape = lambda a: tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)
-        for name, a, want in (("X", X, (B, T + 1, n)),) + tuple(others):
-            if shape(a) != want:
-                raise ValueError(f"{who}: {name} has shape {shape(a)}, expected {want}")
-        sx = shape(x0s)
-        if len(sx) != 3 or sx[0] != B or sx[2] != n or sx[1] < 1:
-            raise ValueError(f"{who}: x0s has shape {sx}, expected ({B}, n_samples >= 1, {n})")
-        S = int(sx[1])
-        if W is not None and shape(W) != (B, S, T, n):
-            raise ValueError(f"{who}: W has shape {shape(W)}, expected {(B, S, T, n)}")
+    # ------------------------------------------------------------------ the closed loop: what the eight methods share
+    # method -> (route, neighbourhood gains?); the C entry is dpilqr_<method>
+    CLOSED_LOOP = {"policy_rollout": ("small", False), "policy_rollout_large": ("large", False), "policy_rollout_dec": ("small", True),
+                   "policy_rollout_dec_team": ("team", True), "policy_advance": ("small", False), "policy_advance_large": ("large", False),
+                   "policy_advance_dec": ("small", True), "policy_advance_dec_team": ("team", True)}
+
+    def _check_route(self, who, route, use):
+        """ValueError, in `who`'s words, unless `route` serves this batch; `use`: the method a too small batch is sent to."""
+        why = route_refusal(route, self.k, self.n_s, self.n_c)
+        if why is not None:
+            text = ROUTE_TEXT_OF.get(who, {}).get(why) or ROUTES[route]["text"][why]
+            raise ValueError(text.format(who=who, use=use, n=self.n_x, k=self.k, n_s=self.n_s, n_c=self.n_c, **ROUTES[route]))
+
+    def _check_u_lim(self, who, u_lim):
         if u_lim is not None:
-            if shape(u_lim) != (2, m):
-                raise ValueError(f"{who}: u_lim has shape {shape(u_lim)}, expected {(2, m)} (lower row, upper row)")
+            if _shape(u_lim) != (2, self.n_u):
+                raise ValueError(f"{who}: u_lim has shape {_shape(u_lim)}, expected {(2, self.n_u)} (lower row, upper row)")
             lim = u_lim.cpu().numpy() if isinstance(u_lim, torch.Tensor) else np.asarray(u_lim, dtype=np.float64)
             if not bool((lim[0] <= lim[1]).all()):
                 raise ValueError(f"{who}: u_lim has a lower limit above its upper limit")
-        return S
 
-    def _policy_stage(self, S, X, U, x0s, W, u_lim, trajectories):
-        """The inputs both rollouts share on the device, and the dict of their outputs."""
-        B, T, n, m = self.B, self.T, self.n_x, self.n_u
+    def _kc_max(self, who, Kc):
+        """Kc (B,T,k,n_c,kc_max*n_s) -> kc_max."""
+        B, T, k, n, ns, nc = self.B, self.T, self.k, self.n_x, self.n_s, self.n_c
+        sk = _shape(Kc)
+        if len(sk) != 5 or sk[:4] != (B, T, k, nc) or sk[4] < ns or sk[4] % ns or sk[4] > n:
+            raise ValueError(f"{who}: Kc has shape {sk}, expected ({B}, {T}, {k}, {nc}, kc_max * {ns}) with 1 <= kc_max <= {k}")
+        return sk[4] // ns
+
+    def _rollout_shapes(self, who, X, U, K, nbr_bits, x0s, W, u_lim, check_masks=True):
+        """Host-side validation of a rollout's arguments, in the order route, Kc, the arrays' shapes, u_lim, the masks; `who` is
+        the method's name in the messages.  Returns (samples per item, kc_max, the masks as a host int64 array): the last two None
+        for dense gains, the last None with check_masks=False.  Only the masks are read, and only when they are a device tensor
+        (B * k words)."""
+        B, T, k, n, m = self.B, self.T, self.k, self.n_x, self.n_u
+        route, dec = self.CLOSED_LOOP[who]
+        self._check_route(who, route, "policy_rollout")
+        kc_max = self._kc_max(who, K) if dec else None
+        others = (("U_ff", U, (B, T, m)), ("nbr_bits", nbr_bits, (B, k))) if dec else (("U", U, (B, T, m)), ("K", K, (B, T, m, n)))
+        for name, a, want in (("X", X, (B, T + 1, n)),) + others:
+            if _shape(a) != want:
+                raise ValueError(f"{who}: {name} has shape {_shape(a)}, expected {want}")
+        sx = _shape(x0s)
+        if len(sx) != 3 or sx[0] != B or sx[2] != n or sx[1] < 1:
+            raise ValueError(f"{who}: x0s has shape {sx}, expected ({B}, n_samples >= 1, {n})")
+        S = int(sx[1])
+        if W is not None and _shape(W) != (B, S, T, n):
+            raise ValueError(f"{who}: W has shape {_shape(W)}, expected {(B, S, T, n)}")
+        self._check_u_lim(who, u_lim)
+        return S, kc_max, self._checked_masks(who, nbr_bits, kc_max) if dec and check_masks else None
+
+    def _rollout(self, who, X, U, K, nbr_bits, x0s, W, u_lim, trajectories, masks_checked=None):
+        """The four rollouts: validate, stage, call dpilqr_<who>, return the dict of outputs."""
+        B, T, k, n, m, ns, nc = self.B, self.T, self.k, self.n_x, self.n_u, self.n_s, self.n_c
+        dec = self.CLOSED_LOOP[who][1]
+        trusted = dec and _masks_trusted(masks_checked, nbr_bits)
+        S, kc_max, bits = self._rollout_shapes(who, X, U, K, nbr_bits, x0s, W, u_lim, check_masks=not trusted)
         X = self._in(X, (B, T + 1, n)); U = self._in(U, (B, T, m)); x0s = self._in(x0s, (B, S, n))
         W = None if W is None else self._in(W, (B, S, T, n))
         u_lim = None if u_lim is None else self._in(u_lim, (2, m))
-        out = dict(J=empty((B, S)), min_sep=empty((B, S)), goal_dist=empty((B, S, self.k)))
+        out = dict(J=empty((B, S)), min_sep=empty((B, S)), goal_dist=empty((B, S, k)))
         if trajectories:
             out["X"] = empty((B, S, T + 1, n)); out["U"] = empty((B, S, T, m))
-        return X, U, x0s, W, u_lim, out
+        K = self._in(K, (B, T, k, nc, kc_max * ns) if dec else (B, T, m, n))
+        gains = ()
+        if dec:
+            bits = nbr_bits.contiguous() if trusted else torch.from_numpy(bits).to(device())
+            gains = (kc_max, ptr(bits))
+        _lib.check(getattr(self._lib, "dpilqr_" + who)(self._d, ptr(X), ptr(U), ptr(K), *gains, S, ptr(x0s), ptr(W), ptr(u_lim),
+                                                       ptr(out.get("X")), ptr(out.get("U")), ptr(out["J"]), ptr(out["min_sep"]),
+                                                       ptr(out["goal_dist"]), stream_handle()))
+        return out
 
     def _policy_shapes(self, X, U, K, x0s, W, u_lim):
         """Host-side validation of policy_rollout's arguments (no device access): returns the number of samples per item."""
-        B, T, n, m = self.B, self.T, self.n_x, self.n_u
-        if n > 60:
-            raise ValueError(f"policy_rollout serves clusters up to n_x = 60, this batch has n_x = {n}")
-        return self._policy_common("policy_rollout", X, x0s, W, u_lim, (("U", U, (B, T, m)), ("K", K, (B, T, m, n))))
+        return self._rollout_shapes("policy_rollout", X, U, K, None, x0s, W, u_lim)[0]
+
+    def _policy_large_shapes(self, X, U, K, x0s, W, u_lim):
+        """Host-side validation of policy_rollout_large's arguments (no device access): returns the number of samples per item."""
+        return self._rollout_shapes("policy_rollout_large", X, U, K, None, x0s, W, u_lim)[0]
+
+    def _policy_dec_shapes(self, X, U_ff, Kc, nbr_bits, x0s, W, u_lim, check_masks=True):
+        """Host-side validation of policy_rollout_dec's arguments: returns (samples per item, kc_max, the masks as a host
+        int64 array -- None with check_masks=False)."""
+        return self._rollout_shapes("policy_rollout_dec", X, U_ff, Kc, nbr_bits, x0s, W, u_lim, check_masks)
+
+    def _policy_dec_team_shapes(self, X, U_ff, Kc, nbr_bits, x0s, W, u_lim, check_masks=True):
+        """Host-side validation of policy_rollout_dec_team's arguments, as _policy_dec_shapes."""
+        return self._rollout_shapes("policy_rollout_dec_team", X, U_ff, Kc, nbr_bits, x0s, W, u_lim, check_masks)
 
     def policy_rollout(self, X, U, K, x0s, W=None, u_lim=None, trajectories=False):
         """The closed-loop ensemble rollout (dpilqr_policy_rollout): every item's feedback policy u_t = U[t] + K[t] (x_t - X[t])
@@ -347,51 +439,13 @@ class ProblemBatch:
         nominal); x0s (B,S,n_x); W (B,S,T,n_x) additive disturbance on x_{t+1} or None; u_lim (2,n_u) lower / upper control
         limits shared by all items or None.  Returns a dict of device tensors: J (B,S), min_sep (B,S), goal_dist (B,S,k) and,
         with trajectories=True, X (B,S,T+1,n_x), U (B,S,T,n_u)."""
-        S = self._policy_shapes(X, U, K, x0s, W, u_lim)
-        X, U, x0s, W, u_lim, out = self._policy_stage(S, X, U, x0s, W, u_lim, trajectories)
-        K = self._in(K, (self.B, self.T, self.n_u, self.n_x))
-        _lib.check(self._lib.dpilqr_policy_rollout(self._d, ptr(X), ptr(U), ptr(K), S, ptr(x0s), ptr(W), ptr(u_lim),
-                                                   ptr(out.get("X")), ptr(out.get("U")), ptr(out["J"]), ptr(out["min_sep"]),
-                                                   ptr(out["goal_dist"]), stream_handle()))
-        return out
-
-    def _policy_large_shapes(self, X, U, K, x0s, W, u_lim):
-        """Host-side validation of policy_rollout_large's arguments (no device access): returns the number of samples per item."""
-        B, T, k, n, m = self.B, self.T, self.k, self.n_x, self.n_u
-        if n <= 60:
-            raise ValueError(f"policy_rollout_large serves clusters of 60 < n_x <= 240, this batch has n_x = {n}: use policy_rollout")
-        if n > 240 or k > 20 or (self.n_s, self.n_c) not in ((4, 2), (6, 3), (12, 4)):
-            raise ValueError(f"policy_rollout_large serves clusters of 60 < n_x <= 240 and k <= 20 of the four-, six- and twelve-state "
-                             f"families, this batch has n_x = {n}, k = {k}, (n_s, n_c) = ({self.n_s}, {self.n_c})")
-        return self._policy_common("policy_rollout_large", X, x0s, W, u_lim, (("U", U, (B, T, m)), ("K", K, (B, T, m, n))))
+        return self._rollout("policy_rollout", X, U, K, None, x0s, W, u_lim, trajectories)
 
     def policy_rollout_large(self, X, U, K, x0s, W=None, u_lim=None, trajectories=False):
         """policy_rollout for large clusters, 60 < n_x <= 240 with k <= 20 (dpilqr_policy_rollout_large): the same arguments and
         the same returned dict.  K[t] (x_t - X[t]) is formed on the fp64 matrix pipe -- the columns in ascending order, one fused
         multiply-add per term -- so a control may differ from policy_rollout's arithmetic in the last bits."""
-        S = self._policy_large_shapes(X, U, K, x0s, W, u_lim)
-        X, U, x0s, W, u_lim, out = self._policy_stage(S, X, U, x0s, W, u_lim, trajectories)
-        K = self._in(K, (self.B, self.T, self.n_u, self.n_x))
-        _lib.check(self._lib.dpilqr_policy_rollout_large(self._d, ptr(X), ptr(U), ptr(K), S, ptr(x0s), ptr(W), ptr(u_lim),
-                                                         ptr(out.get("X")), ptr(out.get("U")), ptr(out["J"]), ptr(out["min_sep"]),
-                                                         ptr(out["goal_dist"]), stream_handle()))
-        return out
-
-    def _policy_dec_shapes(self, X, U_ff, Kc, nbr_bits, x0s, W, u_lim, check_masks=True):
-        """Host-side validation of policy_rollout_dec's arguments: returns (samples per item, kc_max, the masks as a host
-        int64 array -- None with check_masks=False).  Only the masks are read, and only when they are a device tensor
-        (B * k words)."""
-        B, T, k, n, m, ns, nc = self.B, self.T, self.k, self.n_x, self.n_u, self.n_s, self.n_c
-        if n > 60 or k > 20:
-            raise ValueError(f"policy_rollout_dec serves clusters up to n_x = 60 and k = 20, this batch has n_x = {n}, k = {k}")
-        sk = tuple(Kc.shape) if isinstance(Kc, torch.Tensor) else np.shape(Kc)
-        if len(sk) != 5 or sk[:4] != (B, T, k, nc) or sk[4] < ns or sk[4] % ns or sk[4] > n:
-            raise ValueError(f"policy_rollout_dec: Kc has shape {sk}, expected ({B}, {T}, {k}, {nc}, kc_max * {ns}) with 1 <= kc_max <= {k}")
-        kc_max = sk[4] // ns
-        S = self._policy_common("policy_rollout_dec", X, x0s, W, u_lim, (("U_ff", U_ff, (B, T, m)), ("nbr_bits", nbr_bits, (B, k))))
-        if not check_masks:
-            return S, kc_max, None
-        return S, kc_max, self._checked_masks("policy_rollout_dec", nbr_bits, kc_max)
+        return self._rollout("policy_rollout_large", X, U, K, None, x0s, W, u_lim, trajectories)
 
     def _checked_masks(self, who, nbr_bits, kc_max):
         """The masks' contract -- DPILQR_EINVAL of include/dpilqr_policy.h, decided here because the C entry points only
@@ -420,48 +474,14 @@ class ProblemBatch:
         x0s, W, u_lim, trajectories and the returned dict: as policy_rollout, on this (full k-agent) batch.
         masks_checked: the very int64 device tensor given as nbr_bits, if an earlier call has already checked it -- that call's
         read-back of the masks is then not repeated (DistributedPolicy.rollout in a loop)."""
-        trusted = masks_checked is not None and masks_checked is nbr_bits and isinstance(nbr_bits, torch.Tensor) and nbr_bits.dtype == torch.int64
-        S, kc_max, bits = self._policy_dec_shapes(X, U_ff, Kc, nbr_bits, x0s, W, u_lim, check_masks=not trusted)
-        X, U_ff, x0s, W, u_lim, out = self._policy_stage(S, X, U_ff, x0s, W, u_lim, trajectories)
-        Kc = self._in(Kc, (self.B, self.T, self.k, self.n_c, kc_max * self.n_s))
-        bits = nbr_bits.contiguous() if trusted else torch.from_numpy(bits).to(device())
-        _lib.check(self._lib.dpilqr_policy_rollout_dec(self._d, ptr(X), ptr(U_ff), ptr(Kc), kc_max, ptr(bits), S, ptr(x0s), ptr(W),
-                                                       ptr(u_lim), ptr(out.get("X")), ptr(out.get("U")), ptr(out["J"]),
-                                                       ptr(out["min_sep"]), ptr(out["goal_dist"]), stream_handle()))
-        return out
-
-    def _policy_dec_team_shapes(self, X, U_ff, Kc, nbr_bits, x0s, W, u_lim, check_masks=True):
-        """Host-side validation of policy_rollout_dec_team's arguments, as _policy_dec_shapes: (samples per item, kc_max, the
-        masks as a host int64 array -- None with check_masks=False)."""
-        B, T, k, n, m, ns, nc = self.B, self.T, self.k, self.n_x, self.n_u, self.n_s, self.n_c
-        if k > _lib.MAX_AGENTS:
-            raise ValueError(f"policy_rollout_dec_team serves teams of up to {_lib.MAX_AGENTS} agents (a mask is one 64-bit word), "
-                             f"this batch has k = {k}")
-        if ns == 5 and k > 12:
-            raise ValueError(f"policy_rollout_dec_team serves the five-state family up to 12 agents, this batch has k = {k}")
-        sk = tuple(Kc.shape) if isinstance(Kc, torch.Tensor) else np.shape(Kc)
-        if len(sk) != 5 or sk[:4] != (B, T, k, nc) or sk[4] < ns or sk[4] % ns or sk[4] > n:
-            raise ValueError(f"policy_rollout_dec_team: Kc has shape {sk}, expected ({B}, {T}, {k}, {nc}, kc_max * {ns}) with 1 <= kc_max <= {k}")
-        kc_max = sk[4] // ns
-        S = self._policy_common("policy_rollout_dec_team", X, x0s, W, u_lim, (("U_ff", U_ff, (B, T, m)), ("nbr_bits", nbr_bits, (B, k))))
-        if not check_masks:
-            return S, kc_max, None
-        return S, kc_max, self._checked_masks("policy_rollout_dec_team", nbr_bits, kc_max)
+        return self._rollout("policy_rollout_dec", X, U_ff, Kc, nbr_bits, x0s, W, u_lim, trajectories, masks_checked)
 
     def policy_rollout_dec_team(self, X, U_ff, Kc, nbr_bits, x0s, W=None, u_lim=None, trajectories=False, masks_checked=None):
         """policy_rollout_dec for a whole team of up to 64 agents at any n_x (dpilqr_policy_rollout_dec_team): the same arguments,
         the same definition and the same returned dict.  A mask is one 64-bit word (bit 63 a member like any other; int64 masks
         may be negative).  Where both serve a batch, X, U and goal_dist equal policy_rollout_dec's bit for bit, J and min_sep to
         rounding (the stage cost is summed agent by agent)."""
-        trusted = masks_checked is not None and masks_checked is nbr_bits and isinstance(nbr_bits, torch.Tensor) and nbr_bits.dtype == torch.int64
-        S, kc_max, bits = self._policy_dec_team_shapes(X, U_ff, Kc, nbr_bits, x0s, W, u_lim, check_masks=not trusted)
-        X, U_ff, x0s, W, u_lim, out = self._policy_stage(S, X, U_ff, x0s, W, u_lim, trajectories)
-        Kc = self._in(Kc, (self.B, self.T, self.k, self.n_c, kc_max * self.n_s))
-        bits = nbr_bits.contiguous() if trusted else torch.from_numpy(bits).to(device())
-        _lib.check(self._lib.dpilqr_policy_rollout_dec_team(self._d, ptr(X), ptr(U_ff), ptr(Kc), kc_max, ptr(bits), S, ptr(x0s), ptr(W),
-                                                            ptr(u_lim), ptr(out.get("X")), ptr(out.get("U")), ptr(out["J"]),
-                                                            ptr(out["min_sep"]), ptr(out["goal_dist"]), stream_handle()))
-        return out
+        return self._rollout("policy_rollout_dec_team", X, U_ff, Kc, nbr_bits, x0s, W, u_lim, trajectories, masks_checked)
 
     # ------------------------------------------------------------------ the receding-horizon advance
     ADVANCE_STATE = ("x_cur", "n_done", "X_exec", "U_exec", "J_exec", "min_sep", "dist_left", "U_next", "X_next")
@@ -484,24 +504,10 @@ class ProblemBatch:
         """Host-side validation of what policy_advance, policy_advance_dec, policy_advance_large and policy_advance_dec_team
         share (no device access): returns (S, L).  large: the size test is policy_advance_large's; team: the team advance's."""
         B, T, k, n, m = self.B, self.T, self.k, self.n_x, self.n_u
-        if team:
-            if k > _lib.MAX_AGENTS:
-                raise ValueError(f"{who} serves teams of up to {_lib.MAX_AGENTS} agents (a mask is one 64-bit word), "
-                                 f"this batch has k = {k}")
-            if self.n_s == 5 and k > 12:
-                raise ValueError(f"{who} serves the five-state family up to 12 agents, this batch has k = {k}")
-        elif large:
-            if n <= 60:
-                raise ValueError(f"{who} serves clusters of 60 < n_x <= 240, this batch has n_x = {n}: use policy_advance")
-            if n > 240 or k > 20 or (self.n_s, self.n_c) not in ((4, 2), (6, 3), (12, 4)):
-                raise ValueError(f"{who} serves clusters of 60 < n_x <= 240 and k <= 20 of the four-, six- and twelve-state families, "
-                                 f"this batch has n_x = {n}, k = {k}, (n_s, n_c) = ({self.n_s}, {self.n_c})")
-        elif n > 60 or k > 20:
-            raise ValueError(f"{who} serves clusters up to n_x = 60 and k = 20, this batch has n_x = {n}, k = {k}")
-        shape = lambda a: tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)
+        self._check_route(who, "team" if team else "large" if large else "small", "policy_advance")
         for name, a, want in (("X", X, (B, T + 1, n)),) + tuple(others):
-            if a is not None and shape(a) != want:
-                raise ValueError(f"{who}: {name} has shape {shape(a)}, expected {want}")
+            if a is not None and _shape(a) != want:
+                raise ValueError(f"{who}: {name} has shape {_shape(a)}, expected {want}")
         if int(h) != h or not 1 <= h <= T:
             raise ValueError(f"{who}: h = {h}, a round executes 1 .. T = {T} steps")
         if int(n_d) != n_d or not 1 <= n_d <= self.n_s:
@@ -510,7 +516,7 @@ class ProblemBatch:
         missing = [f for f in self.ADVANCE_STATE if not isinstance(get(f), torch.Tensor)]
         if missing:
             raise ValueError(f"{who}: state lacks the device tensors {missing} (ProblemBatch.advance_state makes one)")
-        sx, su = shape(get("x_cur")), shape(get("U_exec"))
+        sx, su = _shape(get("x_cur")), _shape(get("U_exec"))
         if len(sx) != 2 or sx[1] != n or len(su) != 3 or su[1] < 1:
             raise ValueError(f"{who}: state x_cur {sx}, U_exec {su}: expected (S, {n}) and (S, L >= 1, {m})")
         S, L = int(sx[0]), int(su[1])
@@ -518,29 +524,24 @@ class ProblemBatch:
                     U_next=(S, T, m), X_next=(S, T + 1, n))
         for f, w in want.items():
             t = get(f)
-            if shape(t) != w or t.dtype != (torch.int32 if f == "n_done" else torch.float64) or not t.is_contiguous():
-                raise ValueError(f"{who}: state {f} is {shape(t)} {t.dtype}, expected contiguous {w} "
+            if _shape(t) != w or t.dtype != (torch.int32 if f == "n_done" else torch.float64) or not t.is_contiguous():
+                raise ValueError(f"{who}: state {f} is {_shape(t)} {t.dtype}, expected contiguous {w} "
                                  f"{'int32' if f == 'n_done' else 'float64'}")
         if scen is None:
             if S < B:
                 raise ValueError(f"{who}: the state holds {S} scenarios for {B} items and no scen names theirs")
         else:
-            if shape(scen) != (B,):
-                raise ValueError(f"{who}: scen has shape {shape(scen)}, expected {(B,)}")
+            if _shape(scen) != (B,):
+                raise ValueError(f"{who}: scen has shape {_shape(scen)}, expected {(B,)}")
             if not isinstance(scen, torch.Tensor):
                 sc = np.asarray(scen)
                 if sc.dtype.kind not in "iu" or (sc.size and (sc.min() < 0 or sc.max() >= S)) or np.unique(sc).size != sc.size:
                     raise ValueError(f"{who}: scen must name {B} distinct scenarios out of 0 .. {S - 1}")
             elif scen.dtype not in (torch.int32, torch.int64):
                 raise ValueError(f"{who}: scen has dtype {scen.dtype}, expected integers")
-        if W is not None and shape(W) != (S, L, n):
-            raise ValueError(f"{who}: W has shape {shape(W)}, expected {(S, L, n)} (scenarios, capacity, n_x)")
-        if u_lim is not None:
-            if shape(u_lim) != (2, m):
-                raise ValueError(f"{who}: u_lim has shape {shape(u_lim)}, expected {(2, m)} (lower row, upper row)")
-            lim = u_lim.cpu().numpy() if isinstance(u_lim, torch.Tensor) else np.asarray(u_lim, dtype=np.float64)
-            if not bool((lim[0] <= lim[1]).all()):
-                raise ValueError(f"{who}: u_lim has a lower limit above its upper limit")
+        if W is not None and _shape(W) != (S, L, n):
+            raise ValueError(f"{who}: W has shape {_shape(W)}, expected {(S, L, n)} (scenarios, capacity, n_x)")
+        self._check_u_lim(who, u_lim)
         return S, L
 
     def _advance_args(self, X, U, state, scen, W, u_lim, S, L):
@@ -563,33 +564,20 @@ class ProblemBatch:
         and cost are appended at n_done[s] (never past the capacity L), min_sep and dist_left (over n_d coordinates) follow the
         plant, and U_next / X_next receive the plan shifted by the executed steps, the plant's state in front: the next
         round's warm start.  Scenarios not named are not touched.  Returns state."""
-        B, T, n, m = self.B, self.T, self.n_x, self.n_u
-        S, L = self._advance_shapes("policy_advance", X, h, state, scen, W, u_lim, n_d, (("U", U, (B, T, m)), ("K", K, (B, T, m, n))))
-        X, U, scen, W, u_lim, st = self._advance_args(X, U, state, scen, W, u_lim, S, L)
-        K = None if K is None else self._in(K, (B, T, m, n))
-        _lib.check(self._lib.dpilqr_policy_advance(self._d, ptr(X), ptr(U), ptr(K), int(h), ptr(scen), S, L, int(n_d), ptr(W),
-                                                   ptr(u_lim), *st, stream_handle()))
-        return state
+        return self._advance("policy_advance", X, U, K, None, h, state, scen, W, u_lim, n_d)
 
     def policy_advance_large(self, X, U, K, h, state, scen=None, W=None, u_lim=None, n_d=2):
         """policy_advance for large clusters, 60 < n_x <= 240 with k <= 20 (dpilqr_policy_advance_large): the same arguments, the
         same state dict (advance_state) and the same semantics.  K[i] (x - X[i]) is formed on the fp64 matrix pipe as
         policy_rollout_large forms it -- the columns in ascending order, one fused multiply-add per term -- so the executed
         prefix equals that rollout's bit for bit, and may differ from policy_advance's arithmetic in the last bits."""
-        B, T, n, m = self.B, self.T, self.n_x, self.n_u
-        S, L = self._advance_shapes("policy_advance_large", X, h, state, scen, W, u_lim, n_d,
-                                    (("U", U, (B, T, m)), ("K", K, (B, T, m, n))), large=True)
-        X, U, scen, W, u_lim, st = self._advance_args(X, U, state, scen, W, u_lim, S, L)
-        K = None if K is None else self._in(K, (B, T, m, n))
-        _lib.check(self._lib.dpilqr_policy_advance_large(self._d, ptr(X), ptr(U), ptr(K), int(h), ptr(scen), S, L, int(n_d), ptr(W),
-                                                         ptr(u_lim), *st, stream_handle()))
-        return state
+        return self._advance("policy_advance_large", X, U, K, None, h, state, scen, W, u_lim, n_d)
 
     def policy_advance_dec(self, X, U_ff, Kc, nbr_bits, h, state, scen=None, W=None, u_lim=None, n_d=2, masks_checked=None):
         """policy_advance under a distributed solution's policy (dpilqr_policy_advance_dec): X the stitched trajectory, U_ff,
         Kc (B,T,k,n_c,kc_max*n_s) and nbr_bits (B,k) as policy_rollout_dec takes them, masks_checked included.  Kc None: the
         plan U_ff (then U_dec) is executed open loop and the masks are not read."""
-        return self._policy_advance_dec("policy_advance_dec", False, X, U_ff, Kc, nbr_bits, h, state, scen, W, u_lim, n_d, masks_checked)
+        return self._advance("policy_advance_dec", X, U_ff, Kc, nbr_bits, h, state, scen, W, u_lim, n_d, masks_checked)
 
     def policy_advance_dec_team(self, X, U_ff, Kc, nbr_bits, h, state, scen=None, W=None, u_lim=None, n_d=2, masks_checked=None):
         """policy_advance_dec for a whole team of up to 64 agents at any n_x (dpilqr_policy_advance_dec_team): the same
@@ -597,29 +585,31 @@ class ProblemBatch:
         is one 64-bit word (bit 63 a member like any other; int64 masks may be negative).  The executed prefix equals
         policy_rollout_dec_team's bit for bit; where policy_advance_dec serves the batch too, everything but J_exec and min_sep
         equals its results bit for bit, those two to rounding (the stage cost is summed agent by agent)."""
-        return self._policy_advance_dec("policy_advance_dec_team", True, X, U_ff, Kc, nbr_bits, h, state, scen, W, u_lim, n_d, masks_checked)
+        return self._advance("policy_advance_dec_team", X, U_ff, Kc, nbr_bits, h, state, scen, W, u_lim, n_d, masks_checked)
 
-    def _policy_advance_dec(self, who, team, X, U_ff, Kc, nbr_bits, h, state, scen, W, u_lim, n_d, masks_checked):
+    def _advance(self, who, X, U, K, nbr_bits, h, state, scen, W, u_lim, n_d, masks_checked=None):
+        """The four advances: validate (Kc, _advance_shapes, the masks), stage, call dpilqr_<who>, return the state."""
         B, T, k, n, m, ns, nc = self.B, self.T, self.k, self.n_x, self.n_u, self.n_s, self.n_c
-        kc_max = 1
-        if Kc is not None:
-            sk = tuple(Kc.shape) if isinstance(Kc, torch.Tensor) else np.shape(Kc)
-            if len(sk) != 5 or sk[:4] != (B, T, k, nc) or sk[4] < ns or sk[4] % ns or sk[4] > n:
-                raise ValueError(f"{who}: Kc has shape {sk}, expected ({B}, {T}, {k}, {nc}, kc_max * {ns}) with 1 <= kc_max <= {k}")
-            kc_max = sk[4] // ns
-        others = (("U_ff", U_ff, (B, T, m)),) + ((("nbr_bits", nbr_bits, (B, k)),) if Kc is not None else ())
-        S, L = self._advance_shapes(who, X, h, state, scen, W, u_lim, n_d, others, team=team)
-        bits = None
-        if Kc is not None:
-            if nbr_bits is None:
-                raise ValueError(f"{who}: gains without neighbourhood masks")
-            trusted = masks_checked is not None and masks_checked is nbr_bits and isinstance(nbr_bits, torch.Tensor) and nbr_bits.dtype == torch.int64
-            bits = nbr_bits.contiguous() if trusted else torch.from_numpy(self._checked_masks(who, nbr_bits, kc_max)).to(device())
-            Kc = self._in(Kc, (B, T, k, nc, kc_max * ns))
-        X, U_ff, scen, W, u_lim, st = self._advance_args(X, U_ff, state, scen, W, u_lim, S, L)
-        entry = self._lib.dpilqr_policy_advance_dec_team if team else self._lib.dpilqr_policy_advance_dec
-        _lib.check(entry(self._d, ptr(X), ptr(U_ff), ptr(Kc), kc_max, ptr(bits), int(h), ptr(scen), S, L, int(n_d), ptr(W), ptr(u_lim),
-                         *st, stream_handle()))
+        route, dec = self.CLOSED_LOOP[who]
+        kc_max, bits = 1, None
+        if dec:
+            if K is not None:
+                kc_max = self._kc_max(who, K)
+            others = (("U_ff", U, (B, T, m)),) + ((("nbr_bits", nbr_bits, (B, k)),) if K is not None else ())
+        else:
+            others = (("U", U, (B, T, m)), ("K", K, (B, T, m, n)))
+        S, L = self._advance_shapes(who, X, h, state, scen, W, u_lim, n_d, others, large=route == "large", team=route == "team")
+        if K is not None:
+            if dec:
+                if nbr_bits is None:
+                    raise ValueError(f"{who}: gains without neighbourhood masks")
+                trusted = _masks_trusted(masks_checked, nbr_bits)
+                bits = nbr_bits.contiguous() if trusted else torch.from_numpy(self._checked_masks(who, nbr_bits, kc_max)).to(device())
+            K = self._in(K, (B, T, k, nc, kc_max * ns) if dec else (B, T, m, n))
+        X, U, scen, W, u_lim, st = self._advance_args(X, U, state, scen, W, u_lim, S, L)
+        gains = (kc_max, ptr(bits)) if dec else ()
+        _lib.check(getattr(self._lib, "dpilqr_" + who)(self._d, ptr(X), ptr(U), ptr(K), *gains, int(h), ptr(scen), S, L, int(n_d), ptr(W),
+                                                       ptr(u_lim), *st, stream_handle()))
         return state
 
     def cost(self, x, u, terminal=False):

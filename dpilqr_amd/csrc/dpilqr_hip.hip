@@ -808,98 +808,103 @@ int32_t dpilqr_forward_pass(const dpilqr_batch_desc* desc, const double* X, cons
                           n_alpha, Xn, Un, Jn, S, nullptr, nullptr, desc->B, as_stream(stream));
 }
 
+// ---- the closed loop (include/dpilqr_policy.h).  Every entry fills its kind's record (launch.hpp) once; the checks and the
+// launchers take the record.
 // the argument checks the closed-loop rollouts share, under the caller's name (W ... goal_dist may be null)
-static int32_t check_policy_args(const char* who, const dpilqr_batch_desc* desc, int32_t n_samples, const double* X, const double* U,
-                                 const double* K, const double* x0s, const double* J, const double* W, const double* u_lim,
-                                 const double* Xs, const double* Us, const double* min_sep, const double* goal_dist) {
+static int32_t check_policy_args(const char* who, const dpilqr_batch_desc* desc, const PolicyRolloutArgs& a) {
     const int32_t rc = check_desc(desc);
     if (rc) return rc;
-    if (!X || !U || !K || !x0s || !J) return fail(DPILQR_EINVAL, "%s: NULL pointer", who);
-    if (n_samples <= 0) return fail(DPILQR_EINVAL, "%s: n_samples=%d", who, n_samples);
+    const PolicyPlan& p = a.plan;
+    if (!p.X || !p.U || !p.K || !a.x0s || !a.J) return fail(DPILQR_EINVAL, "%s: NULL pointer", who);
+    if (a.n_samples <= 0) return fail(DPILQR_EINVAL, "%s: n_samples=%d", who, a.n_samples);
     // the same alignment rule as the descriptor's pointers: a kernel reading a misaligned one faults the device
+    const double* const doubles[] = {p.X, p.U, p.K, a.x0s, a.J, a.W, a.u_lim, a.Xs, a.Us, a.min_sep, a.goal_dist};
     uintptr_t dbls = 0;
-    for (const double* p : {X, U, K, x0s, J, W, u_lim, Xs, Us, min_sep, goal_dist}) dbls |= reinterpret_cast<uintptr_t>(p);
+    for (const double* q : doubles) dbls |= reinterpret_cast<uintptr_t>(q);
     return dbls % alignof(double) == 0 ? DPILQR_OK : fail(DPILQR_EINVAL, "%s: a device pointer is not aligned to its element type", who);
+}
+
+// the argument checks of the receding-horizon advances (K, W, u_lim, scen may be null)
+static int32_t check_advance_args(const char* who, const dpilqr_batch_desc* desc, const PolicyAdvanceArgs& a) {
+    const int32_t rc = check_desc(desc);
+    if (rc) return rc;
+    const PolicyPlan& p = a.plan;
+    if (!p.X || !p.U || !a.x_cur || !a.n_done || !a.X_exec || !a.U_exec || !a.J_exec || !a.min_sep || !a.dist_left || !a.U_next || !a.X_next)
+        return fail(DPILQR_EINVAL, "%s: NULL pointer", who);
+    if (a.h < 1 || a.h > desc->T) return fail(DPILQR_EINVAL, "%s: h=%d, a round executes 1 .. T = %d steps", who, a.h, desc->T);
+    if (a.L < 1) return fail(DPILQR_EINVAL, "%s: L=%d", who, a.L);
+    if (a.n_d < 1 || a.n_d > desc->n_s) return fail(DPILQR_EINVAL, "%s: n_d=%d, an agent has n_s = %d states", who, a.n_d, desc->n_s);
+    if (a.n_scen < desc->B) return fail(DPILQR_EINVAL, "%s: n_scen=%d for B = %d items", who, a.n_scen, desc->B);
+    const double* const doubles[] = {p.X, p.U, p.K, a.W, a.u_lim, a.x_cur, a.X_exec, a.U_exec, a.J_exec, a.min_sep, a.dist_left, a.U_next, a.X_next};
+    uintptr_t dbls = 0;
+    for (const double* q : doubles) dbls |= reinterpret_cast<uintptr_t>(q);
+    const uintptr_t ints = reinterpret_cast<uintptr_t>(a.scen) | reinterpret_cast<uintptr_t>(a.n_done);
+    return dbls % alignof(double) == 0 && ints % alignof(int32_t) == 0
+               ? DPILQR_OK : fail(DPILQR_EINVAL, "%s: a device pointer is not aligned to its element type", who);
+}
+
+// ... and of the neighbourhood forms: gains come with masks (a rollout's gains are never null: checked above)
+static int32_t check_masks(const char* who, const PolicyPlan& p) {
+    if ((p.K && !p.nbr_bits) || reinterpret_cast<uintptr_t>(p.nbr_bits) % alignof(uint64_t) != 0)
+        return fail(DPILQR_EINVAL, "%s: nbr_bits is a NULL pointer or not aligned to its element type", who);
+    return DPILQR_OK;
 }
 
 int32_t dpilqr_policy_rollout(const dpilqr_batch_desc* desc, const double* X, const double* U, const double* K, int32_t n_samples,
                               const double* x0s, const double* W, const double* u_lim, double* Xs, double* Us, double* J,
                               double* min_sep, double* goal_dist, void* stream) {
-    const int32_t rc = check_policy_args("policy_rollout", desc, n_samples, X, U, K, x0s, J, W, u_lim, Xs, Us, min_sep, goal_dist);
-    return rc ? rc : launch_policy_rollout(*desc, X, U, K, n_samples, x0s, W, u_lim, Xs, Us, J, min_sep, goal_dist, as_stream(stream));
+    const PolicyRolloutArgs a{{X, U, K, 0, nullptr}, n_samples, x0s, W, u_lim, Xs, Us, J, min_sep, goal_dist};
+    const int32_t rc = check_policy_args("policy_rollout", desc, a);
+    return rc ? rc : launch_policy_rollout(*desc, a, as_stream(stream));
 }
 
 int32_t dpilqr_policy_rollout_large(const dpilqr_batch_desc* desc, const double* X, const double* U, const double* K, int32_t n_samples,
                                     const double* x0s, const double* W, const double* u_lim, double* Xs, double* Us, double* J,
                                     double* min_sep, double* goal_dist, void* stream) {
-    const int32_t rc = check_policy_args("policy_rollout_large", desc, n_samples, X, U, K, x0s, J, W, u_lim, Xs, Us, min_sep, goal_dist);
-    return rc ? rc : launch_policy_rollout_large(*desc, X, U, K, n_samples, x0s, W, u_lim, Xs, Us, J, min_sep, goal_dist, as_stream(stream));
+    const PolicyRolloutArgs a{{X, U, K, 0, nullptr}, n_samples, x0s, W, u_lim, Xs, Us, J, min_sep, goal_dist};
+    const int32_t rc = check_policy_args("policy_rollout_large", desc, a);
+    return rc ? rc : launch_policy_rollout_large(*desc, a, as_stream(stream));
 }
 
 int32_t dpilqr_policy_rollout_dec(const dpilqr_batch_desc* desc, const double* X, const double* U_ff, const double* Kc, int32_t kc_max,
                                   const uint64_t* nbr_bits, int32_t n_samples, const double* x0s, const double* W, const double* u_lim,
                                   double* Xs, double* Us, double* J, double* min_sep, double* goal_dist, void* stream) {
-    const int32_t rc = check_policy_args("policy_rollout_dec", desc, n_samples, X, U_ff, Kc, x0s, J, W, u_lim, Xs, Us, min_sep, goal_dist);
-    if (rc) return rc;
-    if (!nbr_bits || reinterpret_cast<uintptr_t>(nbr_bits) % alignof(uint64_t) != 0)
-        return fail(DPILQR_EINVAL, "policy_rollout_dec: nbr_bits is a NULL pointer or not aligned to its element type");
-    return launch_policy_rollout_dec(*desc, X, U_ff, Kc, kc_max, nbr_bits, n_samples, x0s, W, u_lim, Xs, Us, J, min_sep, goal_dist,
-                                     as_stream(stream));
+    const PolicyRolloutArgs a{{X, U_ff, Kc, kc_max, nbr_bits}, n_samples, x0s, W, u_lim, Xs, Us, J, min_sep, goal_dist};
+    int32_t rc = check_policy_args("policy_rollout_dec", desc, a);
+    if (!rc) rc = check_masks("policy_rollout_dec", a.plan);
+    return rc ? rc : launch_policy_rollout_dec(*desc, a, as_stream(stream));
 }
 
 int32_t dpilqr_policy_rollout_dec_team(const dpilqr_batch_desc* desc, const double* X, const double* U_ff, const double* Kc, int32_t kc_max,
                                        const uint64_t* nbr_bits, int32_t n_samples, const double* x0s, const double* W, const double* u_lim,
                                        double* Xs, double* Us, double* J, double* min_sep, double* goal_dist, void* stream) {
-    const int32_t rc = check_policy_args("policy_rollout_dec_team", desc, n_samples, X, U_ff, Kc, x0s, J, W, u_lim, Xs, Us, min_sep, goal_dist);
-    if (rc) return rc;
-    if (!nbr_bits || reinterpret_cast<uintptr_t>(nbr_bits) % alignof(uint64_t) != 0)
-        return fail(DPILQR_EINVAL, "policy_rollout_dec_team: nbr_bits is a NULL pointer or not aligned to its element type");
-    return launch_policy_rollout_dec_team(*desc, X, U_ff, Kc, kc_max, nbr_bits, n_samples, x0s, W, u_lim, Xs, Us, J, min_sep, goal_dist,
-                                          as_stream(stream));
-}
-
-// the argument checks of the two receding-horizon advances (K, W, u_lim, scen may be null)
-static int32_t check_advance_args(const char* who, const dpilqr_batch_desc* desc, const double* X, const double* U, const double* K,
-                                  int32_t h, const int32_t* scen, int32_t n_scen, int32_t L, int32_t n_d, const double* W,
-                                  const double* u_lim, const double* x_cur, const int32_t* n_done, const double* X_exec,
-                                  const double* U_exec, const double* J_exec, const double* min_sep, const double* dist_left,
-                                  const double* U_next, const double* X_next) {
-    const int32_t rc = check_desc(desc);
-    if (rc) return rc;
-    if (!X || !U || !x_cur || !n_done || !X_exec || !U_exec || !J_exec || !min_sep || !dist_left || !U_next || !X_next)
-        return fail(DPILQR_EINVAL, "%s: NULL pointer", who);
-    if (h < 1 || h > desc->T) return fail(DPILQR_EINVAL, "%s: h=%d, a round executes 1 .. T = %d steps", who, h, desc->T);
-    if (L < 1) return fail(DPILQR_EINVAL, "%s: L=%d", who, L);
-    if (n_d < 1 || n_d > desc->n_s) return fail(DPILQR_EINVAL, "%s: n_d=%d, an agent has n_s = %d states", who, n_d, desc->n_s);
-    if (n_scen < desc->B) return fail(DPILQR_EINVAL, "%s: n_scen=%d for B = %d items", who, n_scen, desc->B);
-    uintptr_t dbls = 0;
-    for (const double* p : {X, U, K, W, u_lim, x_cur, X_exec, U_exec, J_exec, min_sep, dist_left, U_next, X_next}) dbls |= reinterpret_cast<uintptr_t>(p);
-    const uintptr_t ints = reinterpret_cast<uintptr_t>(scen) | reinterpret_cast<uintptr_t>(n_done);
-    return dbls % alignof(double) == 0 && ints % alignof(int32_t) == 0
-               ? DPILQR_OK : fail(DPILQR_EINVAL, "%s: a device pointer is not aligned to its element type", who);
+    const PolicyRolloutArgs a{{X, U_ff, Kc, kc_max, nbr_bits}, n_samples, x0s, W, u_lim, Xs, Us, J, min_sep, goal_dist};
+    int32_t rc = check_policy_args("policy_rollout_dec_team", desc, a);
+    if (!rc) rc = check_masks("policy_rollout_dec_team", a.plan);
+    return rc ? rc : launch_policy_rollout_dec_team(*desc, a, as_stream(stream));
 }
 
 int32_t dpilqr_policy_advance(const dpilqr_batch_desc* desc, const double* X, const double* U, const double* K, int32_t h,
                               const int32_t* scen, int32_t n_scen, int32_t L, int32_t n_d, const double* W, const double* u_lim,
                               double* x_cur, int32_t* n_done, double* X_exec, double* U_exec, double* J_exec, double* min_sep,
                               double* dist_left, double* U_next, double* X_next, void* stream) {
-    const int32_t rc = check_advance_args("policy_advance", desc, X, U, K, h, scen, n_scen, L, n_d, W, u_lim, x_cur, n_done, X_exec,
-                                          U_exec, J_exec, min_sep, dist_left, U_next, X_next);
-    return rc ? rc : launch_policy_advance(*desc, X, U, K, 0, nullptr, h, scen, n_scen, L, n_d, W, u_lim, x_cur, n_done, X_exec, U_exec,
-                                           J_exec, min_sep, dist_left, U_next, X_next, as_stream(stream));
+    const PolicyAdvanceArgs a{{X, U, K, 0, nullptr}, h, scen, n_scen, L, n_d, W, u_lim, x_cur, n_done, X_exec, U_exec, J_exec, min_sep,
+                              dist_left, U_next, X_next};
+    const int32_t rc = check_advance_args("policy_advance", desc, a);
+    return rc ? rc : launch_policy_advance(*desc, a, as_stream(stream));
 }
 
 int32_t dpilqr_policy_advance_large(const dpilqr_batch_desc* desc, const double* X, const double* U, const double* K, int32_t h,
                                     const int32_t* scen, int32_t n_scen, int32_t L, int32_t n_d, const double* W, const double* u_lim,
                                     double* x_cur, int32_t* n_done, double* X_exec, double* U_exec, double* J_exec, double* min_sep,
                                     double* dist_left, double* U_next, double* X_next, void* stream) {
-    int32_t rc = check_advance_args("policy_advance_large", desc, X, U, K, h, scen, n_scen, L, n_d, W, u_lim, x_cur, n_done,
-                                    X_exec, U_exec, J_exec, min_sep, dist_left, U_next, X_next);
+    const PolicyAdvanceArgs a{{X, U, K, 0, nullptr}, h, scen, n_scen, L, n_d, W, u_lim, x_cur, n_done, X_exec, U_exec, J_exec, min_sep,
+                              dist_left, U_next, X_next};
+    int32_t rc = check_advance_args("policy_advance_large", desc, a);
     if (rc == DPILQR_EUNSUPPORTED && desc->n_s == 5)      // check_desc's refusal of a large five-state cluster, under this entry's name
         rc = fail(DPILQR_EUNSUPPORTED, "policy_advance_large: the (5, 2) family is served up to n_x = 60, by dpilqr_policy_advance; "
                                        "served here are the (4, 2), (6, 3) and (12, 4) families with 60 < n_x <= 240, k <= 20");
-    return rc ? rc : launch_policy_advance_large(*desc, X, U, K, h, scen, n_scen, L, n_d, W, u_lim, x_cur, n_done, X_exec, U_exec,
-                                                 J_exec, min_sep, dist_left, U_next, X_next, as_stream(stream));
+    return rc ? rc : launch_policy_advance_large(*desc, a, as_stream(stream));
 }
 
 int32_t dpilqr_policy_advance_dec(const dpilqr_batch_desc* desc, const double* X, const double* U_ff, const double* Kc,
@@ -907,15 +912,12 @@ int32_t dpilqr_policy_advance_dec(const dpilqr_batch_desc* desc, const double* X
                                   int32_t L, int32_t n_d, const double* W, const double* u_lim, double* x_cur, int32_t* n_done,
                                   double* X_exec, double* U_exec, double* J_exec, double* min_sep, double* dist_left,
                                   double* U_next, double* X_next, void* stream) {
-    const int32_t rc = check_advance_args("policy_advance_dec", desc, X, U_ff, Kc, h, scen, n_scen, L, n_d, W, u_lim, x_cur, n_done,
-                                          X_exec, U_exec, J_exec, min_sep, dist_left, U_next, X_next);
-    if (rc) return rc;
-    if ((Kc && !nbr_bits) || reinterpret_cast<uintptr_t>(nbr_bits) % alignof(uint64_t) != 0)
-        return fail(DPILQR_EINVAL, "policy_advance_dec: nbr_bits is a NULL pointer or not aligned to its element type");
-    if (kc_max < 1 || kc_max > desc->k)
-        return fail(DPILQR_EUNSUPPORTED, "policy_advance_dec: kc_max=%d, a neighbourhood has 1 .. k = %d members", kc_max, desc->k);
-    return launch_policy_advance(*desc, X, U_ff, Kc, kc_max, nbr_bits, h, scen, n_scen, L, n_d, W, u_lim, x_cur, n_done, X_exec, U_exec,
-                                 J_exec, min_sep, dist_left, U_next, X_next, as_stream(stream));
+    const PolicyAdvanceArgs a{{X, U_ff, Kc, kc_max, nbr_bits}, h, scen, n_scen, L, n_d, W, u_lim, x_cur, n_done, X_exec, U_exec, J_exec,
+                              min_sep, dist_left, U_next, X_next};
+    int32_t rc = check_advance_args("policy_advance_dec", desc, a);
+    if (!rc) rc = check_masks("policy_advance_dec", a.plan);
+    if (!rc) rc = check_kc_max("policy_advance_dec", *desc, kc_max);      // (kc_max = 0 would select the launcher's dense form)
+    return rc ? rc : launch_policy_advance(*desc, a, as_stream(stream));
 }
 
 int32_t dpilqr_policy_advance_dec_team(const dpilqr_batch_desc* desc, const double* X, const double* U_ff, const double* Kc,
@@ -923,13 +925,11 @@ int32_t dpilqr_policy_advance_dec_team(const dpilqr_batch_desc* desc, const doub
                                        int32_t L, int32_t n_d, const double* W, const double* u_lim, double* x_cur, int32_t* n_done,
                                        double* X_exec, double* U_exec, double* J_exec, double* min_sep, double* dist_left,
                                        double* U_next, double* X_next, void* stream) {
-    const int32_t rc = check_advance_args("policy_advance_dec_team", desc, X, U_ff, Kc, h, scen, n_scen, L, n_d, W, u_lim, x_cur, n_done,
-                                          X_exec, U_exec, J_exec, min_sep, dist_left, U_next, X_next);
-    if (rc) return rc;
-    if ((Kc && !nbr_bits) || reinterpret_cast<uintptr_t>(nbr_bits) % alignof(uint64_t) != 0)
-        return fail(DPILQR_EINVAL, "policy_advance_dec_team: nbr_bits is a NULL pointer or not aligned to its element type");
-    return launch_policy_advance_dec_team(*desc, X, U_ff, Kc, kc_max, nbr_bits, h, scen, n_scen, L, n_d, W, u_lim, x_cur, n_done, X_exec,
-                                          U_exec, J_exec, min_sep, dist_left, U_next, X_next, as_stream(stream));
+    const PolicyAdvanceArgs a{{X, U_ff, Kc, kc_max, nbr_bits}, h, scen, n_scen, L, n_d, W, u_lim, x_cur, n_done, X_exec, U_exec, J_exec,
+                              min_sep, dist_left, U_next, X_next};
+    int32_t rc = check_advance_args("policy_advance_dec_team", desc, a);
+    if (!rc) rc = check_masks("policy_advance_dec_team", a.plan);
+    return rc ? rc : launch_policy_advance_dec_team(*desc, a, as_stream(stream));
 }
 
 int32_t dpilqr_alphas(double* alphas_host) {

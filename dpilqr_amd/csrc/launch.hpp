@@ -12,6 +12,8 @@
 // full-team rollout for up to 256 agents), tu_order.hip (the active list ordered by sweep cost) and dpilqr_hip.hip (the C ABI and
 // the solve loop).
 // No device code crosses a file boundary.
+// The closed-loop units (tu_policy*.hip) share the section "the closed loop" below: the routes' limits as named constants and one
+// argument record per kind of entry (PolicyRolloutArgs, PolicyAdvanceArgs) -- the places to change when a limit or an argument does.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -225,48 +227,63 @@ int32_t launch_pairwise_graph(int32_t S, int32_t N, int32_t k, int32_t n_s, cons
                               int32_t* adj, hipStream_t st);
 
 
-// ---- tu_policy.hip: S closed-loop samples per item under u = U + K (x - X) (policy.hpp); n_x <= 60, enqueue only
-int32_t launch_policy_rollout(const dpilqr_batch_desc& D, const double* X, const double* U, const double* K, int32_t n_samples,
-                              const double* x0s, const double* W, const double* u_lim, double* Xs, double* Us, double* J,
-                              double* min_sep, double* goal_dist, hipStream_t st);
+// ---- the closed loop (include/dpilqr_policy.h): the ensemble rollouts and the receding-horizon advances.  This section is the
+// C side's one statement of the routes and of the argument lists -- a further entry, or another limit, is made here and in the
+// route table of dpilqr_amd/batch.py (ROUTES), which tests/test_closed_loop_routes_host.py holds to the launchers' answers.
+// The routes: small -- n_x <= kRouteSmallMaxNx and k <= kRouteSmallMaxK (tu_policy.hip, tu_policy_advance.hip); large --
+// kRouteSmallMaxNx < n_x <= kRouteLargeMaxNx, k <= kRouteLargeMaxK, the (4, 2), (6, 3), (12, 4) families (tu_policy_large.hip,
+// tu_policy_advance_large.hip, whose kernels are built for these bounds: policy_large.hpp); team -- k <= kPolicyTeamAgents
+// (policy_dec_team.hpp: one mask word), whatever n_x is.
+constexpr int kRouteSmallMaxNx = 60, kRouteSmallMaxK = 20, kRouteLargeMaxNx = 240, kRouteLargeMaxK = 20;
+
+// The plan an entry executes: X, U and the gains.  Dense gains K[B][T][n_u][n_x]: kc_max = 0, nbr_bits null; neighbourhood gains
+// Kc[B][T][k][n_c][kc_max * n_s] with the masks nbr_bits[B][k] (policy_dec.hpp).
+struct PolicyPlan {
+    const double *X, *U, *K;
+    int32_t kc_max;
+    const uint64_t* nbr_bits;
+};
+// One record per kind, filled once by the extern "C" entry and unpacked at the kernel launch: a rollout's ...
+struct PolicyRolloutArgs {
+    PolicyPlan plan;
+    int32_t n_samples;
+    const double *x0s, *W, *u_lim;                   // W, u_lim may be null
+    double *Xs, *Us, *J, *min_sep, *goal_dist;       // all but J may be null
+};
+// ... and an advance's (K, scen, W, u_lim may be null)
+struct PolicyAdvanceArgs {
+    PolicyPlan plan;
+    int32_t h;
+    const int32_t* scen;
+    int32_t n_scen, L, n_d;
+    const double *W, *u_lim;
+    double* x_cur;
+    int32_t* n_done;
+    double *X_exec, *U_exec, *J_exec, *min_sep, *dist_left, *U_next, *X_next;
+};
+inline int32_t check_kc_max(const char* who, const dpilqr_batch_desc& D, int32_t kc_max) {
+    return kc_max >= 1 && kc_max <= D.k ? DPILQR_OK
+                                        : fail(DPILQR_EUNSUPPORTED, "%s: kc_max=%d, a neighbourhood has 1 .. k = %d members", who, kc_max, D.k);
+}
+
+// tu_policy.hip: S closed-loop samples per item under u = U + K (x - X) (policy.hpp); the small route, enqueue only
+int32_t launch_policy_rollout(const dpilqr_batch_desc& D, const PolicyRolloutArgs& a, hipStream_t st);
 // ... and of a distributed solution: u_i = U_ff_i + Kc_i (x - X_dec) over agent i's neighbourhood nbr_bits[b][i] (policy_dec.hpp)
-int32_t launch_policy_rollout_dec(const dpilqr_batch_desc& D, const double* X, const double* U_ff, const double* Kc, int32_t kc_max,
-                                  const uint64_t* nbr_bits, int32_t n_samples, const double* x0s, const double* W, const double* u_lim,
-                                  double* Xs, double* Us, double* J, double* min_sep, double* goal_dist, hipStream_t st);
-
-// ---- tu_policy_dec_team.hip: the same closed loop for a whole team of up to 64 agents at any n_x, a thread per (sample, agent), the
+int32_t launch_policy_rollout_dec(const dpilqr_batch_desc& D, const PolicyRolloutArgs& a, hipStream_t st);
+// tu_policy_dec_team.hip: the same closed loop for a whole team of up to 64 agents at any n_x, a thread per (sample, agent), the
 // gains read straight from global memory (policy_dec_team.hpp); enqueue only
-int32_t launch_policy_rollout_dec_team(const dpilqr_batch_desc& D, const double* X, const double* U_ff, const double* Kc, int32_t kc_max,
-                                       const uint64_t* nbr_bits, int32_t n_samples, const double* x0s, const double* W,
-                                       const double* u_lim, double* Xs, double* Us, double* J, double* min_sep, double* goal_dist,
-                                       hipStream_t st);
-
-// ---- tu_policy_advance.hip: the step between two solves of a receding-horizon loop (policy_advance.hpp): h steps of every running
-// scenario's plan, floor(256 / k) items per workgroup, with the loop's bookkeeping; kc_max == 0: the dense form; enqueue only
-int32_t launch_policy_advance(const dpilqr_batch_desc& D, const double* X, const double* U, const double* K, int32_t kc_max,
-                              const uint64_t* nbr_bits, int32_t h, const int32_t* scen, int32_t n_scen, int32_t L, int32_t n_d,
-                              const double* W, const double* u_lim, double* x_cur, int32_t* n_done, double* X_exec, double* U_exec,
-                              double* J_exec, double* min_sep, double* dist_left, double* U_next, double* X_next, hipStream_t st);
-
-// ---- tu_policy_advance_dec_team.hip: the same step under a distributed solution's policy for a whole team of up to 64 agents at
+int32_t launch_policy_rollout_dec_team(const dpilqr_batch_desc& D, const PolicyRolloutArgs& a, hipStream_t st);
+// tu_policy_large.hip: the dense rollout on the large route, K[t] dx on the matrix pipe (policy_large.hpp); enqueue only
+int32_t launch_policy_rollout_large(const dpilqr_batch_desc& D, const PolicyRolloutArgs& a, hipStream_t st);
+// tu_policy_advance.hip: the step between two solves of a receding-horizon loop (policy_advance.hpp): h steps of every running
+// scenario's plan, floor(256 / k) items per workgroup, with the loop's bookkeeping; dense or neighbourhood gains; enqueue only
+int32_t launch_policy_advance(const dpilqr_batch_desc& D, const PolicyAdvanceArgs& a, hipStream_t st);
+// tu_policy_advance_dec_team.hip: the same step under a distributed solution's policy for a whole team of up to 64 agents at
 // any n_x, a thread per (item, agent), the team rollout's arithmetic (policy_advance_dec_team.hpp); Kc null: open loop; enqueue only
-int32_t launch_policy_advance_dec_team(const dpilqr_batch_desc& D, const double* X, const double* U_ff, const double* Kc, int32_t kc_max,
-                                       const uint64_t* nbr_bits, int32_t h, const int32_t* scen, int32_t n_scen, int32_t L, int32_t n_d,
-                                       const double* W, const double* u_lim, double* x_cur, int32_t* n_done, double* X_exec,
-                                       double* U_exec, double* J_exec, double* min_sep, double* dist_left, double* U_next,
-                                       double* X_next, hipStream_t st);
-
-// ---- tu_policy_large.hip: the same rollout for 60 < n_x <= 240, K[t] dx on the matrix pipe (policy_large.hpp); enqueue only
-int32_t launch_policy_rollout_large(const dpilqr_batch_desc& D, const double* X, const double* U, const double* K, int32_t n_samples,
-                                    const double* x0s, const double* W, const double* u_lim, double* Xs, double* Us, double* J,
-                                    double* min_sep, double* goal_dist, hipStream_t st);
-
-// ---- tu_policy_advance_large.hip: the receding-horizon advance for 60 < n_x <= 240, dense gains, one workgroup per item, K[i] dx
-// on the matrix pipe (policy_advance_large.hpp); enqueue only
-int32_t launch_policy_advance_large(const dpilqr_batch_desc& D, const double* X, const double* U, const double* K, int32_t h,
-                                    const int32_t* scen, int32_t n_scen, int32_t L, int32_t n_d, const double* W, const double* u_lim,
-                                    double* x_cur, int32_t* n_done, double* X_exec, double* U_exec, double* J_exec, double* min_sep,
-                                    double* dist_left, double* U_next, double* X_next, hipStream_t st);
+int32_t launch_policy_advance_dec_team(const dpilqr_batch_desc& D, const PolicyAdvanceArgs& a, hipStream_t st);
+// tu_policy_advance_large.hip: the advance on the large route, dense gains, one workgroup per item, K[i] dx on the matrix pipe
+// (policy_advance_large.hpp); enqueue only
+int32_t launch_policy_advance_large(const dpilqr_batch_desc& D, const PolicyAdvanceArgs& a, hipStream_t st);
 
 // ---- tu_rollout_wide.hip: dpilqr_rollout's definition for a full team of up to 256 agents, one workgroup per item
 // (rollout_wide.hpp); X, min_sep, goal_dist may be null; enqueue only

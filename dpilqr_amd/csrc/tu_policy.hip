@@ -13,9 +13,9 @@ struct PolicyGrid { unsigned blocks; int chunks; size_t lds; };      // blocks =
 template <typename Kern>
 static int32_t policy_grid(const char* who, Kern kern, const dpilqr_batch_desc& D, int kc_max, int stage, int32_t n_samples, PolicyGrid& g) {
     const int n = D.k * D.n_s, m = D.k * D.n_c, kw = kc_max * D.n_s;
-    if (n > 60 || D.k > 20)
+    if (n > kRouteSmallMaxNx || D.k > kRouteSmallMaxK)
         return fail(DPILQR_EUNSUPPORTED, "%s: n_x=%d, k=%d, the closed-loop rollout serves clusters up to n_x = 60 and k = 20", who, n, D.k);
-    if (kc_max < 1 || kc_max > D.k) return fail(DPILQR_EUNSUPPORTED, "%s: kc_max=%d, a neighbourhood has 1 .. k = %d members", who, kc_max, D.k);
+    if (const int32_t rc = check_kc_max(who, D, kc_max)) return rc;
     if (m * kw > stage * kPolicyThreads)      // (cannot happen at n_x <= 60, kc_max <= k: the stages are sized for it)
         return fail(DPILQR_EUNSUPPORTED, "%s: K[t] of %d x %d exceeds the %d elements a workgroup copies per step", who, m, kw, stage * kPolicyThreads);
     const int spw = kPolicyThreads / D.k;                      // samples of one item per workgroup
@@ -25,30 +25,27 @@ static int32_t policy_grid(const char* who, Kern kern, const dpilqr_batch_desc& 
     return g.blocks ? allow_lds(kern, g.lds) : DPILQR_OK;
 }
 
-int32_t launch_policy_rollout(const dpilqr_batch_desc& D, const double* X, const double* U, const double* K, int32_t n_samples,
-                              const double* x0s, const double* W, const double* u_lim, double* Xs, double* Us, double* J,
-                              double* min_sep, double* goal_dist, hipStream_t st) {
+int32_t launch_policy_rollout(const dpilqr_batch_desc& D, const PolicyRolloutArgs& a, hipStream_t st) {
     PolicyGrid g;
     DISPATCH_FAMILY_ALL(D.n_s, {
-        const int32_t rc = policy_grid("policy_rollout", k_policy_rollout<NS, NC>, D, D.k, DenseGains<NS, NC>::kStage, n_samples, g);
+        const int32_t rc = policy_grid("policy_rollout", k_policy_rollout<NS, NC>, D, D.k, DenseGains<NS, NC>::kStage, a.n_samples, g);
         if (rc || g.blocks == 0) return rc;
-        hipLaunchKernelGGL((k_policy_rollout<NS, NC>), dim3(g.blocks), dim3(kPolicyThreads), g.lds, st, D, X, U, K, (int)n_samples, g.chunks,
-                           x0s, W, u_lim, Xs, Us, J, min_sep, goal_dist);
+        hipLaunchKernelGGL((k_policy_rollout<NS, NC>), dim3(g.blocks), dim3(kPolicyThreads), g.lds, st, D, a.plan.X, a.plan.U, a.plan.K,
+                           (int)a.n_samples, g.chunks, a.x0s, a.W, a.u_lim, a.Xs, a.Us, a.J, a.min_sep, a.goal_dist);
     })
     HIP_TRY(hipGetLastError());
     return DPILQR_OK;
 }
 
-int32_t launch_policy_rollout_dec(const dpilqr_batch_desc& D, const double* X, const double* U_ff, const double* Kc, int32_t kc_max,
-                                  const uint64_t* nbr_bits, int32_t n_samples, const double* x0s, const double* W, const double* u_lim,
-                                  double* Xs, double* Us, double* J, double* min_sep, double* goal_dist, hipStream_t st) {
+int32_t launch_policy_rollout_dec(const dpilqr_batch_desc& D, const PolicyRolloutArgs& a, hipStream_t st) {
     PolicyGrid g;
     DISPATCH_FAMILY_ALL(D.n_s, {
-        const int32_t rc = policy_grid("policy_rollout_dec", k_policy_rollout_dec<NS, NC>, D, kc_max, CompactGains<NS, NC>::kStage, n_samples, g);
+        const int32_t rc = policy_grid("policy_rollout_dec", k_policy_rollout_dec<NS, NC>, D, a.plan.kc_max, CompactGains<NS, NC>::kStage,
+                                       a.n_samples, g);
         if (rc || g.blocks == 0) return rc;
-        hipLaunchKernelGGL((k_policy_rollout_dec<NS, NC>), dim3(g.blocks), dim3(kPolicyThreads), g.lds, st, D, X, U_ff, Kc, (int)kc_max,
-                           reinterpret_cast<const unsigned long long*>(nbr_bits), (int)n_samples, g.chunks, x0s, W, u_lim, Xs, Us, J, min_sep,
-                           goal_dist);
+        hipLaunchKernelGGL((k_policy_rollout_dec<NS, NC>), dim3(g.blocks), dim3(kPolicyThreads), g.lds, st, D, a.plan.X, a.plan.U, a.plan.K,
+                           (int)a.plan.kc_max, reinterpret_cast<const unsigned long long*>(a.plan.nbr_bits), (int)a.n_samples, g.chunks,
+                           a.x0s, a.W, a.u_lim, a.Xs, a.Us, a.J, a.min_sep, a.goal_dist);
     })
     HIP_TRY(hipGetLastError());
     return DPILQR_OK;

@@ -7,17 +7,17 @@
 namespace dpilqr {
 
 // The families that can exceed 60 states with k <= 20: (4, 2), (6, 3), (12, 4).  Every refusal is answered before any launch.
-int32_t launch_policy_rollout_large(const dpilqr_batch_desc& D, const double* X, const double* U, const double* K, int32_t n_samples,
-                                    const double* x0s, const double* W, const double* u_lim, double* Xs, double* Us, double* J,
-                                    double* min_sep, double* goal_dist, hipStream_t st) {
+static_assert(kRouteLargeMaxNx == kPolicyLargeMaxNx && kRouteLargeMaxK == kPolicyLargeMaxK, "the kernel is built for the route's bounds");
+
+int32_t launch_policy_rollout_large(const dpilqr_batch_desc& D, const PolicyRolloutArgs& a, hipStream_t st) {
     const int n = D.k * D.n_s;
-    if (n <= 60)
+    if (n <= kRouteSmallMaxNx)
         return fail(DPILQR_EUNSUPPORTED, "policy_rollout_large: n_x=%d, clusters up to n_x = 60 are served by dpilqr_policy_rollout", n);
-    if (n > kPolicyLargeMaxNx || D.k > kPolicyLargeMaxK)
+    if (n > kRouteLargeMaxNx || D.k > kRouteLargeMaxK)
         return fail(DPILQR_EUNSUPPORTED, "policy_rollout_large: n_x=%d, k=%d, served are 60 < n_x <= %d with k <= %d", n, D.k,
-                    kPolicyLargeMaxNx, kPolicyLargeMaxK);
+                    kRouteLargeMaxNx, kRouteLargeMaxK);
     const int spw = kPolicyThreads / D.k;                      // samples of one item per workgroup
-    const int64_t chunks = ((int64_t)n_samples + spw - 1) / spw;
+    const int64_t chunks = ((int64_t)a.n_samples + spw - 1) / spw;
     if (chunks * D.B > 0x7fffffffLL) return fail(DPILQR_EUNSUPPORTED, "policy_rollout_large: %lld workgroups", (long long)(chunks * D.B));
     const unsigned blocks = (unsigned)(chunks * D.B);
 #define POLICY_LARGE_CASE(NS_, NC_)                                                                                                  \
@@ -27,8 +27,8 @@ int32_t launch_policy_rollout_large(const dpilqr_batch_desc& D, const double* X,
         const size_t lds = policy_large_lds_bytes(NS_, NC_, D.k);                                                                    \
         const int32_t rc = allow_lds(k_policy_rollout_large<NS_, NC_>, lds);                                                         \
         if (rc) return rc;                                                                                                           \
-        hipLaunchKernelGGL((k_policy_rollout_large<NS_, NC_>), dim3(blocks), dim3(kPolicyThreads), lds, st, D, X, U, K, (int)n_samples, \
-                           (int)chunks, x0s, W, u_lim, Xs, Us, J, min_sep, goal_dist);                                               \
+        hipLaunchKernelGGL((k_policy_rollout_large<NS_, NC_>), dim3(blocks), dim3(kPolicyThreads), lds, st, D, a.plan.X, a.plan.U, a.plan.K, \
+                           (int)a.n_samples, (int)chunks, a.x0s, a.W, a.u_lim, a.Xs, a.Us, a.J, a.min_sep, a.goal_dist);             \
         HIP_TRY(hipGetLastError());                                                                                                  \
         return DPILQR_OK;                                                                                                            \
     }
@@ -40,7 +40,7 @@ int32_t launch_policy_rollout_large(const dpilqr_batch_desc& D, const double* X,
     }
 #undef POLICY_LARGE_CASE
     return fail(DPILQR_EUNSUPPORTED, "policy_rollout_large: the (%d, %d) family cannot exceed 60 states at k <= %d", D.n_s, D.n_c,
-                kPolicyLargeMaxK);
+                kRouteLargeMaxK);
 }
 
 }  // namespace dpilqr

@@ -14,7 +14,7 @@ import torch
 from . import _lib
 from .control import ilqrSolver
 from .device import empty, ptr, stream_handle, to_dev
-from .batch import ProblemBatch
+from .batch import ProblemBatch, route_serves
 from .lowering import describe, is_lowerable, lower_problems
 
 
@@ -292,6 +292,11 @@ class DistributedPolicy:
                                        hints=(k, int(self.X_dec.shape[2]) // k, int(self.U_ff.shape[2]) // k, c["word"]))
         return self._batch
 
+    def _small(self):
+        """The small closed-loop route (batch.ROUTES) serves the full problem; the team route serves every other one."""
+        k = self.desc["k"]
+        return route_serves("small", k, int(self.X_dec.shape[2]) // k, int(self.U_ff.shape[2]) // k)
+
     def rollout(self, x0s, W=None, u_lim=None, trajectories=False):
         """x0s (S, n_samples, n_x) starts per scenario; W (S, n_samples, T, n_x) or None; u_lim (2, n_u) or None.  Returns device
         tensors J, min_sep (S, n_samples), goal_dist (S, n_samples, k) and, with trajectories=True, X, U
@@ -302,7 +307,7 @@ class DistributedPolicy:
         if len(shape) != 3 or shape[0] != S or shape[2] != n or shape[1] < 1:
             raise ValueError(f"DistributedPolicy.rollout: x0s has shape {shape}, expected ({S}, n_samples >= 1, {n})")
         pb = self.batch()
-        run = pb.policy_rollout_dec if n <= 60 and self.desc["k"] <= 20 else pb.policy_rollout_dec_team
+        run = pb.policy_rollout_dec if self._small() else pb.policy_rollout_dec_team
         r = run(self.X_dec, self.U_ff, self.Kc, self.bits, x0s, W=W, u_lim=u_lim, trajectories=trajectories,
                 masks_checked=self._masks_checked)
         self._masks_checked = self.bits
@@ -314,8 +319,7 @@ class DistributedPolicy:
         team=True: a team of n_x > 60 or k > 20 (up to 64 agents) goes through ProblemBatch.policy_advance_dec_team, every
         smaller one through policy_advance_dec as without it."""
         pb = self.batch()
-        n = int(self.X_dec.shape[2])
-        run = pb.policy_advance_dec_team if team and (n > 60 or self.desc["k"] > 20) else pb.policy_advance_dec
+        run = pb.policy_advance_dec_team if team and not self._small() else pb.policy_advance_dec
         r = run(self.X_dec, self.U_ff, self.Kc, self.bits, h, state, scen=scen, W=W, u_lim=u_lim, n_d=n_d,
                 masks_checked=self._masks_checked)
         self._masks_checked = self.bits

@@ -331,7 +331,7 @@ def solve_rhc_closed_loop(problem, x0, N, radius=None, xf=None, U0=None, central
     whatever `team` says.  It is opt-in: without it a larger distributed problem is refused as before.
     Not built: teams of more than 64 agents, fp32, shard=, ignore_ids.  Device problems only."""
     import torch
-    from .batch import ProblemBatch
+    from .batch import ROUTES, ProblemBatch, route_refusal, route_serves
     from .device import to_dev
     from .dispatch import device_constants
     from .lowering import describe, is_lowerable
@@ -342,19 +342,22 @@ def solve_rhc_closed_loop(problem, x0, N, radius=None, xf=None, U0=None, central
     if (J_converge is None) == (dist_converge is None):
         raise ValueError("Must either specify a convergence cost or distance")
     n_x, n_u = problem.dynamics.n_x, problem.dynamics.n_u
-    large = bool(large) and n_x > 60
+    k = problem.n_agents      # (lowerable: one cost and one (n_s, n_c) per agent)
+    n_s, n_c = n_x // k, n_u // k
+    small = route_serves("small", k, n_s, n_c)      # the routes and their limits: batch.ROUTES
+    large = bool(large) and not small
     if team and centralized:
         raise ValueError("solve_rhc_closed_loop: team=True is the distributed loop (centralized=False); a centralized problem of "
                          "60 < n_x <= 240 is served by large=True")
-    team = bool(team) and not large and n_x > 60      # (more than 20 agents have more than 60 states: an agent has at least three)
-    if n_x > 60 and not large and not team:
+    team = bool(team) and not large and not small
+    if not (small or large or team):
         raise ValueError(f"solve_rhc_closed_loop serves problems up to n_x = 60, this one has n_x = {n_x} "
                          "(large=True serves a centralized problem of up to n_x = 240, team=True the distributed loop of a team "
                          "of up to 64 agents)")
     if large and not centralized:
         raise ValueError("solve_rhc_closed_loop: large=True serves the centralized loop only, the distributed loop for problems of "
                          f"more than 60 states is not built (this one has n_x = {n_x})")
-    if large and n_x > 240:
+    if large and n_x > ROUTES["large"]["max_nx"]:
         raise ValueError(f"solve_rhc_closed_loop: large=True serves problems of 60 < n_x <= 240, this one has n_x = {n_x}")
     if not centralized and radius is None:
         raise ValueError("solve_rhc_closed_loop: the distributed solve needs the graph's radius")
@@ -373,17 +376,15 @@ def solve_rhc_closed_loop(problem, x0, N, radius=None, xf=None, U0=None, central
     if not 1 <= h <= N:
         raise ValueError(f"solve_rhc_closed_loop: step_size = {step_size}, a round executes 1 .. N = {N} steps")
     d = describe(problem)
-    k, dt = d["k"], d["dt"]
-    n_s = n_x // k
-    if team:
-        from . import _lib
-        if k > _lib.MAX_AGENTS:
-            raise ValueError(f"solve_rhc_closed_loop is not built for teams of more than {_lib.MAX_AGENTS} agents (this one has {k})")
-        if n_s == 5 and k > 12:
-            raise ValueError(f"solve_rhc_closed_loop: team=True serves the five-state family up to 12 agents, this one has k = {k}")
-    if large and (k > 20 or (n_s, n_u // k) not in ((4, 2), (6, 3), (12, 4))):
+    dt = d["dt"]
+    why = route_refusal("team", k, n_s, n_c) if team else None
+    if why == "beyond":
+        raise ValueError(f"solve_rhc_closed_loop is not built for teams of more than {ROUTES['team']['max_k']} agents (this one has {k})")
+    if why == "family":
+        raise ValueError(f"solve_rhc_closed_loop: team=True serves the five-state family up to 12 agents, this one has k = {k}")
+    if large and not route_serves("large", k, n_s, n_c):      # (n_x lies within the route's bounds: refused above otherwise)
         raise ValueError(f"solve_rhc_closed_loop: large=True serves teams of k <= 20 agents of the four-, six- and twelve-state "
-                         f"families, this one has k = {k}, (n_s, n_c) = ({n_s}, {n_u // k})")
+                         f"families, this one has k = {k}, (n_s, n_c) = ({n_s}, {n_c})")
     if not 1 <= n_d <= n_s:
         raise ValueError(f"solve_rhc_closed_loop: n_d = {n_d}, an agent has {n_s} states")
     solve_kw = solve_kwargs(kwargs, "solve_rhc_closed_loop")
