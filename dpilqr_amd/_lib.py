@@ -112,6 +112,13 @@ SWARM_SIGNATURES = {
     "dpilqr_rollout_wide": (i32, [_DP, vp, vp, vp, vp, vp, vp, vp]),
 }
 
+# ... and of include/dpilqr_swarm_policy.h: the closed-loop rollout of such teams.  Each takes its one-word counterpart's
+# arguments plus n_words (before the stream)
+SWARM_POLICY_SIGNATURES = {
+    "dpilqr_dispatch_stitch_policy_wide": (i32, EXT_SIGNATURES["dpilqr_dispatch_stitch_policy"][1][:-1] + [i32, vp]),
+    "dpilqr_policy_rollout_dec_wide": (i32, EXT_SIGNATURES["dpilqr_policy_rollout_dec_team"][1][:-1] + [i32, vp]),
+}
+
 # ... and of include/dpilqr_order.h: the steps of the solve loop's cost order, stand-alone (csrc/admit_order.hpp)
 ORDER_SIGNATURES = {
     "dpilqr_cost_keys": (i32, [_DP, vp, vp, vp, vp, vp]),
@@ -146,7 +153,7 @@ def load():
             raise ImportError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                               "(hipcc --offload-arch=gfx950).  dpilqr_amd has no CPU fallback.")
         lib = C.CDLL(str(LIB_PATH))
-        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **SWARM_SIGNATURES, **ORDER_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **SWARM_SIGNATURES, **SWARM_POLICY_SIGNATURES, **ORDER_SIGNATURES}.items():
             fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -9,7 +9,7 @@ Python objects on the hot path:
     ilqrSolver._forward_pass   control.py:95-114   -> ProblemBatch.forward_pass
     ilqrSolver.solve           control.py:150-225  -> ProblemBatch.solve
     (no reference counterpart: the feedback policy closed loop)  -> ProblemBatch.policy_rollout, .policy_rollout_large, .policy_rollout_dec,
-                                                                    .policy_rollout_dec_team
+                                                                    .policy_rollout_dec_team, .policy_rollout_dec_wide
     (the step between two solves of a receding-horizon loop on a real plant)  -> ProblemBatch.policy_advance, .policy_advance_large, .policy_advance_dec,
                                                                                  .policy_advance_dec_team
 """
@@ -482,6 +482,74 @@ class ProblemBatch:
         may be negative).  Where both serve a batch, X, U and goal_dist equal policy_rollout_dec's bit for bit, J and min_sep to
         rounding (the stage cost is summed agent by agent)."""
         return self._rollout("policy_rollout_dec_team", X, U_ff, Kc, nbr_bits, x0s, W, u_lim, trajectories, masks_checked)
+
+    # ------------------------------------------------------------------ the closed loop of a team of up to 256 agents
+    def _checked_masks_wide(self, who, nbr_bits, kc_max):
+        """_checked_masks over (B, k, n_words) words -- word w, bit b = agent 64 w + b: own bit set, at most kc_max members, nothing
+        at or past bit k.  Returns the masks as a host int64 array; reads them back when they are a device tensor."""
+        B, k, nw = self.B, self.k, (self.k + 63) // 64
+        bits = nbr_bits.cpu().numpy() if isinstance(nbr_bits, torch.Tensor) else np.asarray(nbr_bits)
+        if bits.dtype.kind not in "iu":
+            raise ValueError(f"{who}: nbr_bits has dtype {bits.dtype}, expected integer bit masks")
+        bits = np.ascontiguousarray(bits.astype(np.uint64)).reshape(B, k, nw)
+        agent = np.arange(k)
+        own = np.uint64(1) << (agent % 64).astype(np.uint64)
+        if not bool(((bits[:, agent, agent // 64] & own[None, :]) != 0).all()):
+            raise ValueError(f"{who}: a neighbourhood mask lacks its agent's own bit (DPILQR_EINVAL)")
+        valid = np.array([(1 << min(max(k - 64 * w, 0), 64)) - 1 for w in range(nw)], dtype=np.uint64)
+        if bool((bits & ~valid[None, None, :]).any()):
+            raise ValueError(f"{who}: a neighbourhood mask has a bit at or past agent k = {k} (DPILQR_EINVAL)")
+        count = np.zeros((B, k), dtype=np.int64)
+        for j in range(64):
+            count += ((bits >> np.uint64(j)) & np.uint64(1)).astype(np.int64).sum(axis=2)
+        if int(count.max(initial=0)) > kc_max:
+            raise ValueError(f"{who}: a neighbourhood mask has {int(count.max())} members, Kc holds kc_max = {kc_max} "
+                             "(DPILQR_EINVAL)")
+        return bits.view(np.int64)
+
+    def policy_rollout_dec_wide(self, X, U_ff, Kc, nbr_bits, x0s, W=None, u_lim=None, trajectories=False, masks_checked=None):
+        """policy_rollout_dec_team for a whole team of up to 256 agents (dpilqr_policy_rollout_dec_wide,
+        include/dpilqr_swarm_policy.h): the same definition and the same returned dict.  nbr_bits (B, k, n_words) integer masks,
+        n_words = ceil(k / 64): word w, bit b = agent 64 w + b; a valid mask has its own bit set, at most kc_max members and
+        nothing at or past bit k.  A neighbourhood is a sub-problem of the distributed solve: kc_max <= min(k, 64), whatever k is.
+        With n_words = 1 every result equals policy_rollout_dec_team's bit for bit.  The other arguments, masks_checked included:
+        as policy_rollout_dec.  fp64 only.  Not built for such teams: the receding-horizon advance."""
+        who = "policy_rollout_dec_wide"
+        B, T, k, n, m, ns, nc = self.B, self.T, self.k, self.n_x, self.n_u, self.n_s, self.n_c
+        if k > _lib.MAX_TEAM:
+            raise ValueError(f"{who} serves teams of up to {_lib.MAX_TEAM} agents, this batch has k = {k}")
+        if ns == 5 and k > ROUTES["team"]["max_k_of_ns"][5]:
+            raise ValueError(f"{who} serves the five-state family up to {ROUTES['team']['max_k_of_ns'][5]} agents, this batch has k = {k}")
+        nw, kc_lim = (k + 63) // 64, min(k, _lib.MAX_AGENTS)
+        sk = _shape(Kc)
+        if len(sk) != 5 or sk[:4] != (B, T, k, nc) or sk[4] < ns or sk[4] % ns or sk[4] > kc_lim * ns:
+            raise ValueError(f"{who}: Kc has shape {sk}, expected ({B}, {T}, {k}, {nc}, kc_max * {ns}) with 1 <= kc_max <= {kc_lim}")
+        kc_max = sk[4] // ns
+        for name, a, want in (("X", X, (B, T + 1, n)), ("U_ff", U_ff, (B, T, m)), ("nbr_bits", nbr_bits, (B, k, nw))):
+            if _shape(a) != want:
+                raise ValueError(f"{who}: {name} has shape {_shape(a)}, expected {want}")
+        sx = _shape(x0s)
+        if len(sx) != 3 or sx[0] != B or sx[2] != n or sx[1] < 1:
+            raise ValueError(f"{who}: x0s has shape {sx}, expected ({B}, n_samples >= 1, {n})")
+        S = int(sx[1])
+        if W is not None and _shape(W) != (B, S, T, n):
+            raise ValueError(f"{who}: W has shape {_shape(W)}, expected {(B, S, T, n)}")
+        self._check_u_lim(who, u_lim)
+        if _masks_trusted(masks_checked, nbr_bits):
+            bits = nbr_bits.contiguous()
+        else:
+            bits = torch.from_numpy(self._checked_masks_wide(who, nbr_bits, kc_max)).to(device())
+        X = self._in(X, (B, T + 1, n)); U_ff = self._in(U_ff, (B, T, m)); x0s = self._in(x0s, (B, S, n))
+        Kc = self._in(Kc, (B, T, k, nc, kc_max * ns))
+        W = None if W is None else self._in(W, (B, S, T, n))
+        u_lim = None if u_lim is None else self._in(u_lim, (2, m))
+        out = dict(J=empty((B, S)), min_sep=empty((B, S)), goal_dist=empty((B, S, k)))
+        if trajectories:
+            out["X"] = empty((B, S, T + 1, n)); out["U"] = empty((B, S, T, m))
+        _lib.check(self._lib.dpilqr_policy_rollout_dec_wide(self._d, ptr(X), ptr(U_ff), ptr(Kc), kc_max, ptr(bits), S, ptr(x0s), ptr(W),
+                                                            ptr(u_lim), ptr(out.get("X")), ptr(out.get("U")), ptr(out["J"]),
+                                                            ptr(out["min_sep"]), ptr(out["goal_dist"]), nw, stream_handle()))
+        return out
 
     # ------------------------------------------------------------------ the receding-horizon advance
     ADVANCE_STATE = ("x_cur", "n_done", "X_exec", "U_exec", "J_exec", "min_sep", "dist_left", "U_next", "X_next")

@@ -811,8 +811,8 @@ int32_t dpilqr_forward_pass(const dpilqr_batch_desc* desc, const double* X, cons
 // ---- the closed loop (include/dpilqr_policy.h).  Every entry fills its kind's record (launch.hpp) once; the checks and the
 // launchers take the record.
 // the argument checks the closed-loop rollouts share, under the caller's name (W ... goal_dist may be null)
-static int32_t check_policy_args(const char* who, const dpilqr_batch_desc* desc, const PolicyRolloutArgs& a) {
-    const int32_t rc = check_desc(desc);
+static int32_t check_policy_args(const char* who, const dpilqr_batch_desc* desc, const PolicyRolloutArgs& a, int max_k = kMaxAgents) {
+    const int32_t rc = check_desc(desc, max_k);
     if (rc) return rc;
     const PolicyPlan& p = a.plan;
     if (!p.X || !p.U || !p.K || !a.x0s || !a.J) return fail(DPILQR_EINVAL, "%s: NULL pointer", who);
@@ -882,6 +882,16 @@ int32_t dpilqr_policy_rollout_dec_team(const dpilqr_batch_desc* desc, const doub
     int32_t rc = check_policy_args("policy_rollout_dec_team", desc, a);
     if (!rc) rc = check_masks("policy_rollout_dec_team", a.plan);
     return rc ? rc : launch_policy_rollout_dec_team(*desc, a, as_stream(stream));
+}
+
+// (include/dpilqr_swarm_policy.h) the team entry's arguments, the masks nbr_bits[B][k][n_words]
+int32_t dpilqr_policy_rollout_dec_wide(const dpilqr_batch_desc* desc, const double* X, const double* U_ff, const double* Kc, int32_t kc_max,
+                                       const uint64_t* nbr_bits, int32_t n_samples, const double* x0s, const double* W, const double* u_lim,
+                                       double* Xs, double* Us, double* J, double* min_sep, double* goal_dist, int32_t n_words, void* stream) {
+    const PolicyRolloutArgs a{{X, U_ff, Kc, kc_max, nbr_bits}, n_samples, x0s, W, u_lim, Xs, Us, J, min_sep, goal_dist};
+    int32_t rc = check_policy_args("policy_rollout_dec_wide", desc, a, DPILQR_MAX_TEAM);
+    if (!rc) rc = check_masks("policy_rollout_dec_wide", a.plan);
+    return rc ? rc : launch_policy_rollout_dec_wide(*desc, a, n_words, as_stream(stream));
 }
 
 int32_t dpilqr_policy_advance(const dpilqr_batch_desc* desc, const double* X, const double* U, const double* K, int32_t h,

@@ -210,4 +210,47 @@ static __global__ void k_stitch_wide(int S, int k, int n_s, int n_c, int T, int 
     }
 }
 
+// k_stitch_policy (frontend.hpp: the definition of Kc and U_ff is the comment above it, unchanged) over n_words words: the owner
+// looked up across the words, the member list (at most kFrontMaxAgents members, ascending) built from them; kc_max <=
+// kFrontMaxAgents (the launcher holds it).  With n_words = 1 Kc and U_ff equal k_stitch_policy's bit for bit.
+static __global__ void k_stitch_policy_wide(int S, int k, int n_s, int n_c, int T, int kc_max, int n_words,
+                                            const unsigned long long* __restrict__ bits, const int32_t* __restrict__ rep,
+                                            const int32_t* __restrict__ size, const int32_t* __restrict__ slot, BucketResults R,
+                                            BucketGains G, const double* __restrict__ X_dec, double* __restrict__ Kc,
+                                            double* __restrict__ U_ff) {
+    const int64_t e = blockIdx.x;             // (s, i)
+    if (e >= (int64_t)S * k) return;
+    int kc, sl, pos;
+    if (!owner_lookup_wide(k, n_words, bits, rep, size, slot, e, kc, sl, pos)) return;
+    if (kc > kc_max || kc > kFrontMaxAgents) return;      // no such bucket was solved (the caller refuses the team)
+    sl -= R.first[kc];
+    if (sl < 0 || sl >= R.count[kc]) return;
+    const int s = (int)(e / k), i = (int)(e % k);
+    __shared__ int mem[kFrontMaxAgents];
+    if (threadIdx.x == 0) {
+        for (int p = 0; p < kFrontMaxAgents; ++p) mem[p] = i;      // (a mask with bits at or past k has fewer members than its size)
+        mask_members(bits + e * n_words, k, n_words, mem);
+    }
+    __syncthreads();
+    const int nx = kc * n_s, nu = kc * n_c, kw = kc_max * n_s;
+    const double* Xb = R.X[kc] + (int64_t)sl * (T + 1) * nx;
+    const double* Ub = R.U[kc] + (int64_t)sl * T * nu;
+    const double* Kb = G.K[kc] + (int64_t)sl * T * nu * nx;
+    for (int q = threadIdx.x; q < T * n_c * kw; q += blockDim.x) {
+        const int t = q / (n_c * kw), r = q - t * n_c * kw, c = r / kw, col = r - c * kw;
+        Kc[(((int64_t)s * T + t) * k + i) * n_c * kw + r] = col < nx ? Kb[((int64_t)t * nu + pos * n_c + c) * nx + col] : 0.0;
+    }
+    for (int q = threadIdx.x; q < T * n_c; q += blockDim.x) {
+        const int t = q / n_c, c = q - t * n_c;
+        const double* Krow = Kb + ((int64_t)t * nu + pos * n_c + c) * nx;
+        const double* Xd = X_dec + ((int64_t)s * (T + 1) + t) * k * n_s;
+        double sum = 0.0;
+        for (int col = 0; col < nx; ++col) {
+            const int p = col / n_s;
+            sum += Krow[col] * (Xd[mem[p] * n_s + (col - p * n_s)] - Xb[(int64_t)t * nx + col]);
+        }
+        U_ff[((int64_t)s * T + t) * k * n_c + i * n_c + c] = Ub[(int64_t)t * nu + pos * n_c + c] + sum;
+    }
+}
+
 }  // namespace dpilqr

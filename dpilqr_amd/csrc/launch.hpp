@@ -7,7 +7,7 @@
 // production), tu_bike.hip (the same for the five-state family, BikeDynamics5D), tu_lsteam.hip (the line search with two
 // wavefronts per item), tu_frontend.hip (the device-side dispatch front / back end), tu_policy.hip (the closed-loop ensemble rollouts),
 // tu_policy_large.hip (the same for n_x > 60), tu_policy_dec_team.hip (a distributed solution's closed loop for teams of up to
-// 64 agents), tu_policy_advance.hip (the receding-horizon advance),
+// 64 agents), tu_policy_dec_wide.hip (the same for teams of up to 256), tu_policy_advance.hip (the receding-horizon advance),
 // tu_policy_advance_large.hip (the same for n_x > 60), tu_rollout_wide.hip (the
 // full-team rollout for up to 256 agents), tu_order.hip (the active list ordered by sweep cost) and dpilqr_hip.hip (the C ABI and
 // the solve loop).
@@ -273,6 +273,9 @@ int32_t launch_policy_rollout_dec(const dpilqr_batch_desc& D, const PolicyRollou
 // tu_policy_dec_team.hip: the same closed loop for a whole team of up to 64 agents at any n_x, a thread per (sample, agent), the
 // gains read straight from global memory (policy_dec_team.hpp); enqueue only
 int32_t launch_policy_rollout_dec_team(const dpilqr_batch_desc& D, const PolicyRolloutArgs& a, hipStream_t st);
+// tu_policy_dec_wide.hip: the same closed loop for a team of up to 256 agents, the masks nbr_bits[B][k][n_words] of
+// n_words = ceil(k / 64) words, a neighbourhood of at most 64 members (policy_dec_wide.hpp); enqueue only
+int32_t launch_policy_rollout_dec_wide(const dpilqr_batch_desc& D, const PolicyRolloutArgs& a, int32_t n_words, hipStream_t st);
 // tu_policy_large.hip: the dense rollout on the large route, K[t] dx on the matrix pipe (policy_large.hpp); enqueue only
 int32_t launch_policy_rollout_large(const dpilqr_batch_desc& D, const PolicyRolloutArgs& a, hipStream_t st);
 // tu_policy_advance.hip: the step between two solves of a receding-horizon loop (policy_advance.hpp): h steps of every running

@@ -214,6 +214,32 @@ int32_t dpilqr_dispatch_stitch_wide(int32_t S, int32_t k, int32_t n_s, int32_t n
     return DPILQR_OK;
 }
 
+int32_t dpilqr_dispatch_stitch_policy_wide(int32_t S, int32_t k, int32_t n_s, int32_t n_c, int32_t T, int32_t kc_max,
+                                           const uint64_t* bits, const int32_t* rep, const int32_t* size, const int32_t* slot,
+                                           const dpilqr_bucket_results* results, const dpilqr_bucket_gains* gains,
+                                           const double* X_dec, double* Kc, double* U_ff, int32_t n_words, void* stream) {
+    const int32_t rc = check_wide("dispatch_stitch_policy_wide", k, n_words);
+    if (rc) return rc;
+    if (S < 0 || n_s < 1 || n_c < 1 || T < 1 || !bits || !rep || !size || !slot || !results || !gains || !X_dec || !Kc || !U_ff)
+        return fail(DPILQR_EINVAL, "dispatch_stitch_policy_wide: bad argument");
+    const int kc_lim = k < kFrontMaxAgents ? k : kFrontMaxAgents;
+    if (kc_max < 1 || kc_max > kc_lim)
+        return fail(DPILQR_EINVAL, "dispatch_stitch_policy_wide: kc_max=%d, a neighbourhood has 1 .. min(k, %d) = %d members", kc_max,
+                    kFrontMaxAgents, kc_lim);
+    for (int kc = 1; kc <= kc_lim; ++kc) {
+        if (results->count[kc] <= 0) continue;
+        if (kc > kc_max) return fail(DPILQR_EINVAL, "dispatch_stitch_policy_wide: sub-problems of %d agents, kc_max=%d", kc, kc_max);
+        if (!results->X[kc] || !results->U[kc] || !gains->K[kc]) return fail(DPILQR_EINVAL, "dispatch_stitch_policy_wide: NULL results of size %d", kc);
+    }
+    if (S == 0) return DPILQR_OK;
+    BucketGains G;
+    memcpy(&G, gains, sizeof(G));
+    hipLaunchKernelGGL(k_stitch_policy_wide, dim3((unsigned)((int64_t)S * k)), dim3(128), 0, as_stream(stream), S, k, n_s, n_c, T, kc_max,
+                       n_words, reinterpret_cast<const unsigned long long*>(bits), rep, size, slot, to_internal(results), G, X_dec, Kc, U_ff);
+    HIP_TRY(hipGetLastError());
+    return DPILQR_OK;
+}
+
 int32_t dpilqr_random_setup(int32_t S, int64_t seed0, int32_t k, int32_t n_s, int32_t n_d, double var, double energy,
                             double* x0, double* xf, void* stream) {
     if (S < 0 || k < 1 || k > kFrontMaxAgents || n_d < 1 || n_d > 3 || n_s < n_d || !x0 || !xf || seed0 < 0 ||

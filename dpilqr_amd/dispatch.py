@@ -118,7 +118,8 @@ class ScenarioFrontEnd:
     n_words = ceil(k / 64) words and `bits` is (S*k, n_words); k <= 64 takes the one-word entries and `bits` is (S*k,), as ever
     (wide=True puts such a team on the wide entries with n_words = 1: the same arrays, bit for bit).
     A cluster (sub-problem) has at most 64 agents in either form: a populated cluster size beyond that is a ValueError before any
-    solve.  Not built for wide teams: stitch_policy, pack_rows / scatter_rows (policy=True, shard=)."""
+    solve.  The policy of a wide team is stitched by stitch_policy_wide (policy="wide").  Not built for wide teams: stitch_policy,
+    pack_rows / scatter_rows (policy=True, shard=)."""
 
     def __init__(self, d, X, U, radius, xf, ignore=None, wide=None):
         self.lib = _lib.load()
@@ -245,6 +246,26 @@ class ScenarioFrontEnd:
                                                           ptr(U_ff), stream_handle()))
         return Kc, U_ff, kc_max
 
+    def stitch_policy_wide(self, solved, gains, X_dec):
+        """stitch_policy over the multi-word masks of a front end on the wide entries (dpilqr_dispatch_stitch_policy_wide,
+        include/dpilqr_swarm_policy.h): the same arguments, the same definition and the same returned (Kc, U_ff, kc_max), for teams
+        of up to 256 agents.  With n_words = 1 (a team of up to 64 agents made with wide=True) Kc and U_ff equal stitch_policy's bit
+        for bit."""
+        import ctypes as C
+        if not self.wide:
+            raise ValueError("stitch_policy_wide needs a front end on the wide entries (ScenarioFrontEnd(..., wide=True))")
+        S, k, ns, nc, T = self.S, self.k, self.n_s, self.n_c, self.T
+        kc_max = max(self.sizes(), default=1)
+        Kc = empty((S, T, k, nc, kc_max * ns)); U_ff = empty((S, T, k * nc))
+        R = self.results_struct(solved)
+        G = _lib.BucketGains()
+        for kc, K in gains.items():
+            G.K[kc] = K.data_ptr()
+        _lib.check(self.lib.dpilqr_dispatch_stitch_policy_wide(S, k, ns, nc, T, kc_max, ptr(self.bits), ptr(self.rep), ptr(self.size),
+                                                               ptr(self.slot), C.addressof(R), C.addressof(G), ptr(X_dec), ptr(Kc),
+                                                               ptr(U_ff), self.n_words, stream_handle()))
+        return Kc, U_ff, kc_max
+
     def pack_rows(self, solved, count_only=False, pad_to=None):
         """One row [s*k+i | X columns | U columns] per (scenario, agent) whose sub-problem is in `solved`; returns
         (rows or None, n_rows).  Rows beyond n_rows (up to pad_to) carry index -1."""
@@ -275,10 +296,13 @@ class DistributedPolicy:
     """The feedback policy of a distributed solution of S scenarios, on the device (solve_scenarios_distributed(policy=True)):
     agent i of scenario s applies u_i = U_ff[s][t][i] + Kc[s][t][i] (x - X_dec[s][t]) over its neighbourhood bits[s][i].
     X_dec (S,T+1,n_x), U_ff (S,T,n_u), Kc (S,T,k,n_c,kc_max*n_s), bits (S,k) int64 masks, kc_max; desc: the problem's
-    description (lowering.describe), xf (S,n_x) the scenarios' goals."""
+    description (lowering.describe), xf (S,n_x) the scenarios' goals.
+    wide=True (solve_scenarios_distributed(policy="wide"), teams of up to 256 agents): bits is (S,k,n_words) -- word w, bit b =
+    agent 64 w + b --, rollout goes through ProblemBatch.policy_rollout_dec_wide and advance is not built."""
 
-    def __init__(self, desc, xf, X_dec, U_ff, Kc, bits, kc_max):
+    def __init__(self, desc, xf, X_dec, U_ff, Kc, bits, kc_max, wide=False):
         self.desc, self.xf, self.X_dec, self.U_ff, self.Kc, self.bits, self.kc_max = desc, xf, X_dec, U_ff, Kc, bits, int(kc_max)
+        self.wide = bool(wide)      # bits (S,k,n_words): the rollout is ProblemBatch.policy_rollout_dec_wide, whatever the size
         self._batch = self._masks_checked = None
 
     def batch(self):
@@ -307,7 +331,7 @@ class DistributedPolicy:
         if len(shape) != 3 or shape[0] != S or shape[2] != n or shape[1] < 1:
             raise ValueError(f"DistributedPolicy.rollout: x0s has shape {shape}, expected ({S}, n_samples >= 1, {n})")
         pb = self.batch()
-        run = pb.policy_rollout_dec if self._small() else pb.policy_rollout_dec_team
+        run = pb.policy_rollout_dec_wide if self.wide else pb.policy_rollout_dec if self._small() else pb.policy_rollout_dec_team
         r = run(self.X_dec, self.U_ff, self.Kc, self.bits, x0s, W=W, u_lim=u_lim, trajectories=trajectories,
                 masks_checked=self._masks_checked)
         self._masks_checked = self.bits
@@ -317,7 +341,10 @@ class DistributedPolicy:
         """Execute h steps of every scenario's policy on the plant state kept in `state` and shift the plan
         (ProblemBatch.policy_advance_dec on the full problem): the step between two solves of a receding-horizon loop.
         team=True: a team of n_x > 60 or k > 20 (up to 64 agents) goes through ProblemBatch.policy_advance_dec_team, every
-        smaller one through policy_advance_dec as without it."""
+        smaller one through policy_advance_dec as without it.  Not built: the advance of a wide policy (policy="wide")."""
+        if self.wide:
+            raise ValueError(f"DistributedPolicy.advance: the wide advance is not built (policy='wide' serves the closed-loop rollout "
+                             f"only; this team has {self.desc['k']} agents)")
         pb = self.batch()
         run = pb.policy_advance_dec_team if team and not self._small() else pb.policy_advance_dec
         r = run(self.X_dec, self.U_ff, self.Kc, self.bits, h, state, scen=scen, W=W, u_lim=u_lim, n_d=n_d,
@@ -342,14 +369,17 @@ def solve_scenarios_distributed(problem, X, U, radius, xf=None, window=None, con
             sub-problem solves needs; the solves themselves are the same (with policy=True also the bucket's gains K)
     policy: also take the feedback policy of the distributed solution -- one backward pass per bucket at its solved (X, U) with
             regularisation policy_mu (ilqrSolver.closed_loop takes its gains the same way), stitched on the device into
-            info["policy"], a DistributedPolicy; not with `shard` or `ignore_ids`
+            info["policy"], a DistributedPolicy; not with `shard` or `ignore_ids`.  policy="wide": the same for ANY team of up to
+            256 agents, over the wide front end (multi-word masks; wide=True where k <= 64) and stitch_policy_wide:
+            info["policy"].bits is (S, k, n_words), .rollout runs ProblemBatch.policy_rollout_dec_wide, .advance raises
     returns X_dec (S, T+1, n_x), U_dec (S, T, n_u), J_full (S,), info (clusters as bit masks, counts) -- NumPy arrays, or
     device tensors with device_out=True; with `shard` the unstitched (front end, solved slices) pair instead.
 
     Teams of 64 < k <= 256 agents are served too (multi-word masks, the full-team rollout ProblemBatch.rollout_wide for J_full):
     info["cluster_bits"] is then (S, k, ceil(k / 64)) -- word w, bit b = agent 64 w + b -- instead of (S, k).  Every cluster still
-    has at most 64 agents and lies within the solver's own limits.  Not built for such teams: policy=True and shard= (each a
-    ValueError before any device work).
+    has at most 64 agents and lies within the solver's own limits.  The closed-loop rollout of such a team: policy="wide".  Not
+    built for such teams: policy=True and shard= (each a ValueError before any device work), the receding-horizon advance of a
+    wide policy, fp32.
     """
     from .sharding import shard_bounds
     if policy and (shard is not None or ignore_ids):
@@ -357,8 +387,11 @@ def solve_scenarios_distributed(problem, X, U, radius, xf=None, window=None, con
                          "scenario needs its sub-problem's gains on this device)")
     d = desc if desc is not None else describe(problem)      # desc: the caller's description (its device constants are reused)
     k = d["k"]
-    if k > _lib.MAX_AGENTS and (policy or shard is not None):
-        raise ValueError(f"solve_scenarios_distributed: {'policy=True' if policy else 'shard='} is not built for teams of more than "
+    if isinstance(policy, str) and policy != "wide":
+        raise ValueError(f"solve_scenarios_distributed: policy={policy!r}, expected False, True or 'wide'")
+    wide_policy = isinstance(policy, str)
+    if k > _lib.MAX_AGENTS and ((policy and not wide_policy) or shard is not None):
+        raise ValueError(f"solve_scenarios_distributed: {'policy=True' if policy and not wide_policy else 'shard='} is not built for teams of more than "
                          f"{_lib.MAX_AGENTS} agents (this one has {k})")
     ignore = None
     if ignore_ids:
@@ -367,7 +400,7 @@ def solve_scenarios_distributed(problem, X, U, radius, xf=None, window=None, con
     solve_kw = solve_kwargs(kwargs, "solve_scenarios_distributed")
     from time import perf_counter as pc
     t0 = pc()
-    fe = ScenarioFrontEnd(d, X, U, radius, xf, ignore)
+    fe = ScenarioFrontEnd(d, X, U, radius, xf, ignore, wide=True if wide_policy else None)
     t_front = pc() - t0                      # uploads, graph, de-duplication, bucket sort, the one host read
     S, T = fe.S, fe.T
     sizes = fe.sizes()
@@ -421,10 +454,12 @@ def solve_scenarios_distributed(problem, X, U, radius, xf=None, window=None, con
     info["seconds"]["stitch_and_rollout"] = pc() - t0
     if policy:
         t0 = pc()
-        Kc, U_ff, kc_max = fe.stitch_policy(solved, {kc: r[6] for kc, r in results if r is not None}, X_dec)
+        Kc, U_ff, kc_max = (fe.stitch_policy_wide if wide_policy else fe.stitch_policy)(
+            solved, {kc: r[6] for kc, r in results if r is not None}, X_dec)
         torch.cuda.synchronize()
         info["seconds"]["stitch_policy"] = pc() - t0
-        info["policy"] = DistributedPolicy(d, fe.xf, X_dec, U_ff, Kc, fe.bits.reshape(S, k), kc_max)
+        info["policy"] = DistributedPolicy(d, fe.xf, X_dec, U_ff, Kc, fe.bits.reshape((S, k, fe.n_words) if wide_policy else (S, k)),
+                                           kc_max, wide=wide_policy)
     info["cluster_bits"] = fe.bits.cpu().numpy().reshape((S, k, fe.n_words) if fe.wide else (S, k))
     if device_out:
         return X_dec, U_dec, J, info

@@ -69,13 +69,15 @@ def solve_distributed(problem, X, U, radius, ignore_ids=None, pool=None, verbose
     return X_dec, U_dec, J_full, solve_info
 
 
-def closed_loop_distributed(problem, X, U, radius, x0s, W=None, u_lim=None, mu=0.0, trajectories=False, **solve_kwargs):
+def closed_loop_distributed(problem, X, U, radius, x0s, W=None, u_lim=None, mu=0.0, trajectories=False, wide=False, **solve_kwargs):
     """The closed loop of solve_distributed's solution for one scenario: solve the sub-problems from (X, U) as
     solve_scenarios_distributed does, take every sub-problem's gains from one backward pass at its solution (regularisation
     mu, as ilqrSolver.closed_loop), and run the agents' own feedback laws -- each over its neighbourhood only -- on the full
     problem from the starts x0s (n_samples, n_x).  W (n_samples, N, n_x): additive disturbance; u_lim (2, n_u): control limits.
     Returns host arrays: J, min_sep (n_samples,), goal_dist (n_samples, k), X_dec, U_dec of the solve and, with
-    trajectories=True, X (n_samples, N+1, n_x), U (n_samples, N, n_u).  Device problems only."""
+    trajectories=True, X (n_samples, N+1, n_x), U (n_samples, N, n_u).  Device problems only.
+    wide=True: solve_scenarios_distributed(policy="wide") -- any team of up to 256 agents, multi-word neighbourhood masks,
+    ProblemBatch.policy_rollout_dec_wide; the default serves teams of up to 64 agents as ever."""
     from .lowering import is_lowerable
     if not is_lowerable(problem):
         raise NotImplementedError("closed_loop_distributed runs the policy on the device and needs a problem built from the "
@@ -88,7 +90,7 @@ def closed_loop_distributed(problem, X, U, radius, x0s, W=None, u_lim=None, mu=0
         raise ValueError(f"closed_loop_distributed: x0s has shape {x0s.shape}, expected (n_samples, {n_x})")
     if U.ndim != 2 or X.shape[1] != n_x or X.shape[0] not in (1, U.shape[0] + 1):
         raise ValueError(f"closed_loop_distributed: X {X.shape}, U {U.shape}: expected (N+1 or 1, {n_x}) and (N, n_u)")
-    X_dec, U_dec, _, info = solve_scenarios_distributed(problem, X[None], U[None], radius, device_out=True, policy=True,
+    X_dec, U_dec, _, info = solve_scenarios_distributed(problem, X[None], U[None], radius, device_out=True, policy="wide" if wide else True,
                                                         policy_mu=float(mu), **solve_kwargs)
     r = info["policy"].rollout(x0s[None], W=None if W is None else np.asarray(W, dtype=np.float64)[None], u_lim=u_lim,
                                trajectories=trajectories)

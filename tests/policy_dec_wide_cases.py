@@ -1,0 +1,228 @@
+"""Shared by tests/test_gpu_policy_dec_wide.py, tests/test_policy_dec_wide_host.py and scripts/policy_dec_wide_checks.py: the cases
+of the closed-loop rollout for teams of up to 256 agents (dpilqr_policy_rollout_dec_wide, csrc/policy_dec_wide.hpp) and the CPU
+side of their check.  Nothing here touches the GPU.
+
+Reused: policy_cases.Case, make_batch, bound_of, difference, MAX_UNCHECKED and the conditions of policy_cases.CaseRef;
+policy_dec_team_cases.separation.  policy_dec_cases.DecCaseRef is NOT reused: its item 0 has a full mask (a wide neighbourhood has
+at most 64 members) and its gains come from a dense backward pass of the whole team, O(n_x^3) at n_x = 1024.  Instead:
+  nominal      per item, the full-team oracle rollout of (x0, U0)
+  memberships  seeded.  Item 0: every neighbourhood has exactly kc_max members drawn from the whole team, and every seventh agent
+               has the word edges {63, 64, k - 1, 0} forced in (distinct, minus the agent itself, as many as kc_max - 1 holds,
+               the list rotated from agent to agent so that every edge is used).  Item 1: every agent alone.  Item 2: sizes
+               1 .. kc_max - 1, asymmetric.
+  gains        agent a's gains are its rows of the oracle's backward_pass (mu = policy_cases.MU) of the sub-problem of its own
+               neighbourhood at the restricted nominal -- what a distributed solve produces
+  reference    every agent's law over its members, then the full-team Problem.step / .cost and the vectorised separation
+  sensitivity  the reference rerun at +-PERTURB on x0s, X, U and the gains, as policy_cases.CaseRef._run does; the bound of a
+               sample is bound_of(spread) = max(1e-9, 100 spread)
+
+The shapes are the smallest at which THIS kernel can go wrong (T = 12, B = 3 as in policy_cases):
+  wide-dint4-k65-S4        the first k past one word; 3 samples per workgroup, so the second workgroup holds one; odd k
+  wide-dint4_uni4-k86-S3   2 samples per workgroup; mixed models; per-item weights; even k
+  wide-car3-k65-S3         the three-state family
+  wide-quad12-k65-S2       the register peak; n_dims = 3
+  wide-dint4-k129-S2       three words, the last holding one agent; 1 sample per workgroup
+  wide-dint4-k256-S2       four words; bit 255; all 256 lanes; the offset k / 2
+sigma and radius were set on the CPU reference alone so that every case meets the conditions of
+tests/test_policy_dec_wide_host.py::test_case_conditions.  A six-state case (66 quadcopters, kc_max 4, radius 0.06) was tried:
+with S = 3 and two seeds it moves 0.33 of its samples at sigma 0.6 and 0.44 at 0.7 (0.5 is asked), and leaves 0.11 to 0.22 of
+them without a bound at sigma 0.7 to 0.8 (0.05 is the cap), so it is not among the cases; the six-state instantiation is covered by the n_words = 1 cross-check against policy_rollout_dec_team on
+team-quad6-k21-S13."""
+import numpy as np
+
+from tests import linesearch_cases as lc
+from tests import policy_cases as pc
+from tests import policy_dec_team_cases as tc
+
+T, B = pc.T, pc.B
+EDGES = (63, 64, -1, 0)      # -1: agent k - 1
+
+
+class WideCase(pc.Case):
+    def __init__(self, name, models, S, sigma, radius, kc_max, **kw):
+        super().__init__(name, models, S, sigma, radius, **kw)
+        self.kc_max = kc_max
+        self.n_words = (self.k + 63) // 64
+
+
+CASES = [
+    WideCase("wide-dint4-k65-S4", [0] * 65, 4, 0.3, 0.3, 8, seed=65),
+    WideCase("wide-dint4_uni4-k86-S3", [0, 3] * 43, 3, 0.3, 0.3, 5, weights="per_item", seed=86),
+    WideCase("wide-car3-k65-S3", [2] * 65, 3, 0.2, 0.15, 4, seed=66),
+    WideCase("wide-quad12-k65-S2", [7] * 65, 2, 0.2, 0.6, 3, seed=67),
+    WideCase("wide-dint4-k129-S2", [0] * 129, 2, 0.3, 0.3, 8, seed=129),
+    WideCase("wide-dint4-k256-S2", [0] * 256, 2, 0.3, 0.3, 8, seed=256),
+]
+IDS = [c.id for c in CASES]
+
+
+def make_members(case):
+    """members[b][a]: agent a's neighbourhood in item b, ascending, a among them (the module docstring)."""
+    k, kc_max = case.k, case.kc_max
+    rng = np.random.default_rng(8800 + case.seed)
+    edges = [e % k for e in EDGES]
+    item0 = []
+    for a in range(k):
+        forced = []
+        if a % 7 == 0:
+            rot = (a // 7) % len(edges)
+            for e in edges[rot:] + edges[:rot]:
+                if e != a and e not in forced and len(forced) < kc_max - 1:
+                    forced.append(e)
+        rest = [j for j in range(k) if j != a and j not in forced]
+        drawn = rng.choice(rest, size=kc_max - 1 - len(forced), replace=False).tolist()
+        item0.append(sorted([a] + forced + drawn))
+    item1 = [[a] for a in range(k)]
+    while True:
+        item2 = []
+        for a in range(k):
+            size = int(rng.integers(1, kc_max))      # 1 .. kc_max - 1
+            others = rng.choice([j for j in range(k) if j != a], size=size - 1, replace=False).tolist()
+            item2.append(sorted([a] + others))
+        if any(j != a and a not in item2[j] for a in range(k) for j in item2[a]):      # asymmetric
+            return [item0, item1, item2]
+
+
+def words_of(members, k):
+    """(B, k, n_words) uint64: word w, bit b = agent 64 w + b."""
+    nw = (k + 63) // 64
+    bits = np.zeros((len(members), k, nw), dtype=np.uint64)
+    for b, item in enumerate(members):
+        for a, mem in enumerate(item):
+            for j in mem:
+                bits[b, a, j // 64] |= np.uint64(1) << np.uint64(j % 64)
+    return bits
+
+
+def members_of(words, k):
+    """The inverse of words_of for one (k, n_words) item: lists of members, word by word, lowest bit first."""
+    return [[64 * w + b for w in range(words.shape[1]) for b in range(64) if (int(words[a, w]) >> b) & 1 and 64 * w + b < k]
+            for a in range(k)]
+
+
+def gather_index(members, ns, kc_max):
+    """(k, kc_max * ns) state columns of every agent's members in ascending order (columns past them: 0) and the 0 / 1 mask of
+    the columns in use."""
+    k = len(members)
+    idx = np.zeros((k, kc_max * ns), dtype=np.int64); used = np.zeros((k, kc_max * ns))
+    for a, mem in enumerate(members):
+        cols = np.concatenate([np.arange(j * ns, (j + 1) * ns) for j in mem])
+        idx[a, :cols.size] = cols; used[a, :cols.size] = 1.0
+    return idx, used
+
+
+def apply_law(U_t, Kc_t, idx, used, dx):
+    """u = U_ff[t] + Kc[t] (x - X[t]) over every agent's members: Kc_t (k, n_c, kc_max * n_s), columns out of use ignored."""
+    Kz = np.where(used[:, None, :] != 0.0, Kc_t, 0.0)
+    return U_t + np.einsum("acj,aj->ac", Kz, dx[idx] * used).reshape(-1)
+
+
+def dense_gains(Kc_t, members, ns, nc):
+    """(n_u, n_x) with agent a's compact blocks at its members' columns, zero elsewhere (small teams only: the layout test)."""
+    k = len(members)
+    K = np.zeros((k * nc, k * ns))
+    for a, mem in enumerate(members):
+        for p, j in enumerate(mem):
+            K[a * nc:(a + 1) * nc, j * ns:(j + 1) * ns] = Kc_t[a, :, p * ns:(p + 1) * ns]
+    return K
+
+
+def sub_gains(batch, i, X, U, mem, ns, nc):
+    """The oracle's backward pass of the sub-problem of the agents `mem` of item i at the restricted nominal: (T, kc n_c, kc n_s)."""
+    b = batch
+    xc = np.concatenate([np.arange(j * ns, (j + 1) * ns) for j in mem])
+    uc = np.concatenate([np.arange(j * nc, (j + 1) * nc) for j in mem])
+    p = lc.orc.Problem([b["models"][j] for j in mem], [b["n_dims"][j] for j in mem], b["xf"][i][xc], b["Qi"][i][mem], b["Ri"][i][mem],
+                       b["Qfi"][i][mem], b["radius"], b["dt"], b["T"])
+    return np.asarray(p.backward_pass(np.ascontiguousarray(X[:, xc]), np.ascontiguousarray(U[:, uc]), pc.MU)[0])
+
+
+def compact_gains(batch, X, U, members, ns, nc, kc_max, fill=np.nan):
+    """Kc (B, T, k, n_c, kc_max * n_s): agent a's rows of its own sub-problem's gains, the columns past its members `fill`."""
+    k = len(members[0])
+    Kc = np.full((B, T, k, nc, kc_max * ns), fill, dtype=np.float64)
+    for i in range(B):
+        cache = {}
+        for a, mem in enumerate(members[i]):
+            key = tuple(mem)
+            if key not in cache:
+                cache[key] = sub_gains(batch, i, X[i], U[i], mem, ns, nc)
+            pos = mem.index(a)
+            Kc[i, :, a, :, :len(mem) * ns] = cache[key][:, pos * nc:(pos + 1) * nc, :]
+    return Kc
+
+
+def ref_sample(p, batch, i, X, U, Kc, idx, used, x0, W=None, u_lim=None):
+    """policy_dec_team_cases.ref_sample with every agent's law applied over its members (Kc (T, k, n_c, kc_max n_s))."""
+    k, n_dims = len(batch["models"]), batch["n_dims"]
+    ns = X.shape[1] // k
+    Tn = U.shape[0]
+    Xs = np.zeros((Tn + 1, X.shape[1])); Us = np.zeros_like(U)
+    Xs[0] = x0
+    J, sep = 0.0, tc.separation(Xs[0], k, ns, n_dims)
+    for t in range(Tn):
+        u = apply_law(U[t], Kc[t], idx, used, Xs[t] - X[t])
+        if u_lim is not None:
+            u = np.where(u < u_lim[0], u_lim[0], np.where(u > u_lim[1], u_lim[1], u))
+        Us[t] = u
+        J += float(p.cost(Xs[t], u))
+        Xs[t + 1] = p.step(Xs[t], u)
+        if W is not None:
+            Xs[t + 1] += W[t]
+        sep = min(sep, tc.separation(Xs[t + 1], k, ns, n_dims))
+    J += float(p.cost(Xs[-1], np.zeros(U.shape[1]), terminal=True))
+    e = (Xs[-1] - batch["xf"][i]).reshape(k, ns)
+    nd = np.asarray(n_dims)
+    goal = np.sqrt(np.sum((e ** 2) * (np.arange(ns)[None, :] < nd[:, None]), axis=1))
+    return dict(X=Xs, U=Us, J=J, min_sep=sep, goal_dist=goal)
+
+
+class WideCaseRef(pc.CaseRef):
+    """The CPU side of one case (the module docstring); the variants, limits and conditions are policy_cases.CaseRef's."""
+
+    def __init__(self, case):
+        self.case, self.batch = case, pc.make_batch(case)
+        b, ns, nc = self.batch, case.ns, case.nc
+        self.members = make_members(case)
+        self.words = words_of(self.members, case.k)
+        self.problems = [pc.item_problem(b, i) for i in range(B)]
+        self.U = b["U0"]
+        self.X = np.stack([np.asarray(self.problems[i].rollout(b["x0"][i], self.U[i])[0]) for i in range(B)])
+        self.Kc = compact_gains(b, self.X, self.U, self.members, ns, nc, case.kc_max)
+        self.K = np.nan_to_num(self.Kc, nan=0.0)      # (what the sensitivity runs scale)
+        self.index = [gather_index(self.members[i], ns, case.kc_max) for i in range(B)]
+        self.ref, self.spread = {}, {}
+        self._run("plain")
+        allU = np.stack([[self.ref["plain"][i][s]["U"] for s in range(case.S)] for i in range(B)])
+        flat = allU.reshape(-1, allU.shape[-1])
+        self.u_lim = np.stack([np.quantile(flat, pc.QUANTILES[0], axis=0), np.quantile(flat, pc.QUANTILES[1], axis=0)])
+        self._run("W"); self._run("u_lim")
+        self.J_nom = np.array([self._sample(i, self.X[i][0])["J"] for i in range(B)])
+
+    def _sample(self, i, x0, W=None, lim=None, e=0.0):
+        idx, used = self.index[i]
+        return ref_sample(self.problems[i], self.batch, i, self.X[i] * (1 + e), self.U[i] * (1 - e), self.K[i] * (1 - e), idx, used,
+                          x0 * (1 + e), W, lim)
+
+    def _run(self, variant):
+        b, S = self.batch, self.case.S
+        W, lim = self.args(variant)
+        self.ref[variant] = [[None] * S for _ in range(B)]
+        self.spread[variant] = np.zeros((B, S))
+        for i in range(B):
+            for s in range(S):
+                Ws = None if W is None else W[i, s]
+                r = self._sample(i, b["x0s"][i, s], Ws, lim)
+                self.ref[variant][i][s] = r
+                self.spread[variant][i, s] = max(pc.difference(self._sample(i, b["x0s"][i, s], Ws, lim, e=sg * lc.PERTURB), r)
+                                                 for sg in (1.0, -1.0))
+
+
+_REFS = {}
+
+
+def case_ref(case):
+    """Computed once per case and shared (never modified) by the tests that need it."""
+    if case.id not in _REFS:
+        _REFS[case.id] = WideCaseRef(case)
+    return _REFS[case.id]
