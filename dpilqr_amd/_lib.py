@@ -119,6 +119,13 @@ SWARM_POLICY_SIGNATURES = {
     "dpilqr_policy_rollout_dec_wide": (i32, EXT_SIGNATURES["dpilqr_policy_rollout_dec_team"][1][:-1] + [i32, vp]),
 }
 
+# ... and of include/dpilqr_swarm_advance.h: the receding-horizon advance of such teams (the team entry's arguments plus n_words
+# before the stream) and the cost of a point of one (dpilqr_cost_eval's arguments)
+SWARM_ADVANCE_SIGNATURES = {
+    "dpilqr_policy_advance_dec_wide": (i32, EXT_SIGNATURES["dpilqr_policy_advance_dec_team"][1][:-1] + [i32, vp]),
+    "dpilqr_cost_eval_wide": (i32, list(SIGNATURES["dpilqr_cost_eval"][1])),
+}
+
 # ... and of include/dpilqr_order.h: the steps of the solve loop's cost order, stand-alone (csrc/admit_order.hpp)
 ORDER_SIGNATURES = {
     "dpilqr_cost_keys": (i32, [_DP, vp, vp, vp, vp, vp]),
@@ -153,7 +160,8 @@ def load():
             raise ImportError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                               "(hipcc --offload-arch=gfx950).  dpilqr_amd has no CPU fallback.")
         lib = C.CDLL(str(LIB_PATH))
-        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **SWARM_SIGNATURES, **SWARM_POLICY_SIGNATURES, **ORDER_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **SWARM_SIGNATURES, **SWARM_POLICY_SIGNATURES, **SWARM_ADVANCE_SIGNATURES,
+                                   **ORDER_SIGNATURES}.items():
             fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

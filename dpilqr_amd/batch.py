@@ -11,7 +11,8 @@ Python objects on the hot path:
     (no reference counterpart: the feedback policy closed loop)  -> ProblemBatch.policy_rollout, .policy_rollout_large, .policy_rollout_dec,
                                                                     .policy_rollout_dec_team, .policy_rollout_dec_wide
     (the step between two solves of a receding-horizon loop on a real plant)  -> ProblemBatch.policy_advance, .policy_advance_large, .policy_advance_dec,
-                                                                                 .policy_advance_dec_team
+                                                                                 .policy_advance_dec_team, .policy_advance_dec_wide
+    (GameCost.__call__ at a few points, teams of up to 64 / 256 agents)  -> ProblemBatch.cost, .cost_wide
 """
 import ctypes as C
 import os
@@ -513,7 +514,7 @@ class ProblemBatch:
         n_words = ceil(k / 64): word w, bit b = agent 64 w + b; a valid mask has its own bit set, at most kc_max members and
         nothing at or past bit k.  A neighbourhood is a sub-problem of the distributed solve: kc_max <= min(k, 64), whatever k is.
         With n_words = 1 every result equals policy_rollout_dec_team's bit for bit.  The other arguments, masks_checked included:
-        as policy_rollout_dec.  fp64 only.  Not built for such teams: the receding-horizon advance."""
+        as policy_rollout_dec.  fp64 only.  The receding-horizon advance of such teams: policy_advance_dec_wide."""
         who = "policy_rollout_dec_wide"
         B, T, k, n, m, ns, nc = self.B, self.T, self.k, self.n_x, self.n_u, self.n_s, self.n_c
         if k > _lib.MAX_TEAM:
@@ -568,11 +569,13 @@ class ProblemBatch:
                     dist_left=torch.full((S, self.k), float("nan"), dtype=torch.float64, device=x0.device),
                     U_next=zeros((S, self.T, self.n_u)), X_next=zeros((S, self.T + 1, self.n_x)))
 
-    def _advance_shapes(self, who, X, h, state, scen, W, u_lim, n_d, others, large=False, team=False):
+    def _advance_shapes(self, who, X, h, state, scen, W, u_lim, n_d, others, large=False, team=False, wide=False):
         """Host-side validation of what policy_advance, policy_advance_dec, policy_advance_large and policy_advance_dec_team
-        share (no device access): returns (S, L).  large: the size test is policy_advance_large's; team: the team advance's."""
+        share (no device access): returns (S, L).  large: the size test is policy_advance_large's; team: the team advance's;
+        wide: none here (policy_advance_dec_wide lies outside the route table and has tested its own limits)."""
         B, T, k, n, m = self.B, self.T, self.k, self.n_x, self.n_u
-        self._check_route(who, "team" if team else "large" if large else "small", "policy_advance")
+        if not wide:
+            self._check_route(who, "team" if team else "large" if large else "small", "policy_advance")
         for name, a, want in (("X", X, (B, T + 1, n)),) + tuple(others):
             if a is not None and _shape(a) != want:
                 raise ValueError(f"{who}: {name} has shape {_shape(a)}, expected {want}")
@@ -680,14 +683,58 @@ class ProblemBatch:
                                                        ptr(u_lim), *st, stream_handle()))
         return state
 
+    def policy_advance_dec_wide(self, X, U_ff, Kc, nbr_bits, h, state, scen=None, W=None, u_lim=None, n_d=2, masks_checked=None):
+        """policy_advance_dec_team for a whole team of up to 256 agents (dpilqr_policy_advance_dec_wide,
+        include/dpilqr_swarm_advance.h): the same arguments, the same state dict (advance_state) and the same semantics, with
+        policy_rollout_dec_wide's arithmetic and masks: nbr_bits (B, k, n_words), n_words = ceil(k / 64), word w, bit b =
+        agent 64 w + b; kc_max <= min(k, 64).  The executed prefix equals policy_rollout_dec_wide's bit for bit; with
+        n_words = 1 all nine state fields equal policy_advance_dec_team's bit for bit.  Kc None: the plan U_ff (then U_dec) is
+        executed open loop and the masks are not read.  fp64 only."""
+        who = "policy_advance_dec_wide"
+        B, T, k, n, m, ns, nc = self.B, self.T, self.k, self.n_x, self.n_u, self.n_s, self.n_c
+        if k > _lib.MAX_TEAM:
+            raise ValueError(f"{who} serves teams of up to {_lib.MAX_TEAM} agents, this batch has k = {k}")
+        if ns == 5 and k > ROUTES["team"]["max_k_of_ns"][5]:
+            raise ValueError(f"{who} serves the five-state family up to {ROUTES['team']['max_k_of_ns'][5]} agents, this batch has k = {k}")
+        nw, kc_lim, kc_max, bits = (k + 63) // 64, min(k, _lib.MAX_AGENTS), 1, None
+        others = (("U_ff", U_ff, (B, T, m)),)
+        if Kc is not None:
+            sk = _shape(Kc)
+            if len(sk) != 5 or sk[:4] != (B, T, k, nc) or sk[4] < ns or sk[4] % ns or sk[4] > kc_lim * ns:
+                raise ValueError(f"{who}: Kc has shape {sk}, expected ({B}, {T}, {k}, {nc}, kc_max * {ns}) with 1 <= kc_max <= {kc_lim}")
+            kc_max = sk[4] // ns
+            if nbr_bits is None:
+                raise ValueError(f"{who}: gains without neighbourhood masks")
+            others += (("nbr_bits", nbr_bits, (B, k, nw)),)
+        S, L = self._advance_shapes(who, X, h, state, scen, W, u_lim, n_d, others, wide=True)
+        if Kc is not None:
+            if _masks_trusted(masks_checked, nbr_bits):
+                bits = nbr_bits.contiguous()
+            else:
+                bits = torch.from_numpy(self._checked_masks_wide(who, nbr_bits, kc_max)).to(device())
+            Kc = self._in(Kc, (B, T, k, nc, kc_max * ns))
+        X, U_ff, scen, W, u_lim, st = self._advance_args(X, U_ff, state, scen, W, u_lim, S, L)
+        _lib.check(self._lib.dpilqr_policy_advance_dec_wide(self._d, ptr(X), ptr(U_ff), ptr(Kc), kc_max, ptr(bits), int(h), ptr(scen), S, L,
+                                                            int(n_d), ptr(W), ptr(u_lim), *st, nw, stream_handle()))
+        return state
+
     def cost(self, x, u, terminal=False):
         """GameCost.__call__ at n_pts points per item: x (B,n_pts,n_x), u (B,n_pts,n_u) -> (B,n_pts)."""
+        return self._cost("dpilqr_cost_eval", x, u, terminal)
+
+    def cost_wide(self, x, u, terminal=False):
+        """cost for a team of up to 256 agents (dpilqr_cost_eval_wide, include/dpilqr_swarm_advance.h): the same kernel, so at
+        k <= 64 the same bits.  One thread per point walks all k (k - 1) / 2 pairs: for a few points (a loop's terminal cost)."""
+        if self.k > _lib.MAX_TEAM:
+            raise ValueError(f"cost_wide serves teams of up to {_lib.MAX_TEAM} agents, this batch has k = {self.k}")
+        return self._cost("dpilqr_cost_eval_wide", x, u, terminal)
+
+    def _cost(self, entry, x, u, terminal):
         x = to_dev(x).reshape(self.B, -1, self.n_x).contiguous()
         n_pts = x.shape[1]
         u = to_dev(u).reshape(self.B, n_pts, self.n_u).contiguous()
         out = empty((self.B, n_pts))
-        _lib.check(self._lib.dpilqr_cost_eval(self._d, n_pts, ptr(x), ptr(u), int(bool(terminal)), ptr(out),
-                                              stream_handle()))
+        _lib.check(getattr(self._lib, entry)(self._d, n_pts, ptr(x), ptr(u), int(bool(terminal)), ptr(out), stream_handle()))
         return out
 
     # ------------------------------------------------------------------ whole solve

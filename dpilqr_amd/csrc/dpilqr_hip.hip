@@ -825,8 +825,8 @@ static int32_t check_policy_args(const char* who, const dpilqr_batch_desc* desc,
 }
 
 // the argument checks of the receding-horizon advances (K, W, u_lim, scen may be null)
-static int32_t check_advance_args(const char* who, const dpilqr_batch_desc* desc, const PolicyAdvanceArgs& a) {
-    const int32_t rc = check_desc(desc);
+static int32_t check_advance_args(const char* who, const dpilqr_batch_desc* desc, const PolicyAdvanceArgs& a, int max_k = kMaxAgents) {
+    const int32_t rc = check_desc(desc, max_k);
     if (rc) return rc;
     const PolicyPlan& p = a.plan;
     if (!p.X || !p.U || !a.x_cur || !a.n_done || !a.X_exec || !a.U_exec || !a.J_exec || !a.min_sep || !a.dist_left || !a.U_next || !a.X_next)
@@ -940,6 +940,29 @@ int32_t dpilqr_policy_advance_dec_team(const dpilqr_batch_desc* desc, const doub
     int32_t rc = check_advance_args("policy_advance_dec_team", desc, a);
     if (!rc) rc = check_masks("policy_advance_dec_team", a.plan);
     return rc ? rc : launch_policy_advance_dec_team(*desc, a, as_stream(stream));
+}
+
+// (include/dpilqr_swarm_advance.h) the team entry's arguments, the masks nbr_bits[B][k][n_words]
+int32_t dpilqr_policy_advance_dec_wide(const dpilqr_batch_desc* desc, const double* X, const double* U_ff, const double* Kc,
+                                       int32_t kc_max, const uint64_t* nbr_bits, int32_t h, const int32_t* scen, int32_t n_scen,
+                                       int32_t L, int32_t n_d, const double* W, const double* u_lim, double* x_cur, int32_t* n_done,
+                                       double* X_exec, double* U_exec, double* J_exec, double* min_sep, double* dist_left,
+                                       double* U_next, double* X_next, int32_t n_words, void* stream) {
+    const PolicyAdvanceArgs a{{X, U_ff, Kc, kc_max, nbr_bits}, h, scen, n_scen, L, n_d, W, u_lim, x_cur, n_done, X_exec, U_exec, J_exec,
+                              min_sep, dist_left, U_next, X_next};
+    int32_t rc = check_advance_args("policy_advance_dec_wide", desc, a, DPILQR_MAX_TEAM);
+    if (!rc) rc = check_masks("policy_advance_dec_wide", a.plan);
+    return rc ? rc : launch_policy_advance_dec_wide(*desc, a, n_words, as_stream(stream));
+}
+
+// ... and dpilqr_cost_eval for such a team: k_cost_eval has no structure sized by the one-word limit
+int32_t dpilqr_cost_eval_wide(const dpilqr_batch_desc* desc, int32_t n_pts, const double* x, const double* u,
+                              int32_t terminal, double* cost, void* stream) {
+    int32_t rc = check_desc(desc, DPILQR_MAX_TEAM);
+    if (rc) return rc;
+    if (n_pts < 0 || !x || !u || !cost) return fail(DPILQR_EINVAL, "cost_eval_wide: bad argument");
+    if ((int64_t)desc->B * n_pts == 0) return DPILQR_OK;
+    return launch_cost_eval(*desc, n_pts, x, u, terminal, cost, as_stream(stream));
 }
 
 int32_t dpilqr_alphas(double* alphas_host) {

@@ -284,6 +284,9 @@ int32_t launch_policy_advance(const dpilqr_batch_desc& D, const PolicyAdvanceArg
 // tu_policy_advance_dec_team.hip: the same step under a distributed solution's policy for a whole team of up to 64 agents at
 // any n_x, a thread per (item, agent), the team rollout's arithmetic (policy_advance_dec_team.hpp); Kc null: open loop; enqueue only
 int32_t launch_policy_advance_dec_team(const dpilqr_batch_desc& D, const PolicyAdvanceArgs& a, hipStream_t st);
+// tu_policy_advance_dec_wide.hip: the same step for a team of up to 256 agents, the masks nbr_bits[B][k][n_words] of
+// n_words = ceil(k / 64) words, a neighbourhood of at most 64 members (policy_advance_dec_wide.hpp); Kc null: open loop; enqueue only
+int32_t launch_policy_advance_dec_wide(const dpilqr_batch_desc& D, const PolicyAdvanceArgs& a, int32_t n_words, hipStream_t st);
 // tu_policy_advance_large.hip: the advance on the large route, dense gains, one workgroup per item, K[i] dx on the matrix pipe
 // (policy_advance_large.hpp); enqueue only
 int32_t launch_policy_advance_large(const dpilqr_batch_desc& D, const PolicyAdvanceArgs& a, hipStream_t st);

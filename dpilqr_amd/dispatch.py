@@ -298,7 +298,8 @@ class DistributedPolicy:
     X_dec (S,T+1,n_x), U_ff (S,T,n_u), Kc (S,T,k,n_c,kc_max*n_s), bits (S,k) int64 masks, kc_max; desc: the problem's
     description (lowering.describe), xf (S,n_x) the scenarios' goals.
     wide=True (solve_scenarios_distributed(policy="wide"), teams of up to 256 agents): bits is (S,k,n_words) -- word w, bit b =
-    agent 64 w + b --, rollout goes through ProblemBatch.policy_rollout_dec_wide and advance is not built."""
+    agent 64 w + b --, rollout goes through ProblemBatch.policy_rollout_dec_wide and advance(..., wide=True) through
+    ProblemBatch.policy_advance_dec_wide."""
 
     def __init__(self, desc, xf, X_dec, U_ff, Kc, bits, kc_max, wide=False):
         self.desc, self.xf, self.X_dec, self.U_ff, self.Kc, self.bits, self.kc_max = desc, xf, X_dec, U_ff, Kc, bits, int(kc_max)
@@ -337,16 +338,22 @@ class DistributedPolicy:
         self._masks_checked = self.bits
         return r
 
-    def advance(self, h, state, scen=None, W=None, u_lim=None, n_d=2, team=False):
+    def advance(self, h, state, scen=None, W=None, u_lim=None, n_d=2, team=False, wide=False):
         """Execute h steps of every scenario's policy on the plant state kept in `state` and shift the plan
         (ProblemBatch.policy_advance_dec on the full problem): the step between two solves of a receding-horizon loop.
         team=True: a team of n_x > 60 or k > 20 (up to 64 agents) goes through ProblemBatch.policy_advance_dec_team, every
-        smaller one through policy_advance_dec as without it.  Not built: the advance of a wide policy (policy="wide")."""
-        if self.wide:
-            raise ValueError(f"DistributedPolicy.advance: the wide advance is not built (policy='wide' serves the closed-loop rollout "
-                             f"only; this team has {self.desc['k']} agents)")
+        smaller one through policy_advance_dec as without it.  wide=True: the advance of a wide policy (policy="wide", teams of
+        up to 256 agents), ProblemBatch.policy_advance_dec_wide whatever the size; it is opt-in, a wide policy without it is
+        refused, and so is wide=True on a one-word policy."""
+        if self.wide and not wide:
+            raise ValueError(f"DistributedPolicy.advance: the wide advance is not built into the default route (policy='wide' holds "
+                             f"multi-word masks; this team has {self.desc['k']} agents): pass wide=True, which runs "
+                             "ProblemBatch.policy_advance_dec_wide")
+        if wide and not self.wide:
+            raise ValueError("DistributedPolicy.advance: wide=True needs a wide policy (masks of shape (S, k, n_words)): solve with "
+                             "policy=\"wide\"")
         pb = self.batch()
-        run = pb.policy_advance_dec_team if team and not self._small() else pb.policy_advance_dec
+        run = pb.policy_advance_dec_wide if wide else pb.policy_advance_dec_team if team and not self._small() else pb.policy_advance_dec
         r = run(self.X_dec, self.U_ff, self.Kc, self.bits, h, state, scen=scen, W=W, u_lim=u_lim, n_d=n_d,
                 masks_checked=self._masks_checked)
         self._masks_checked = self.bits
@@ -371,15 +378,15 @@ def solve_scenarios_distributed(problem, X, U, radius, xf=None, window=None, con
             regularisation policy_mu (ilqrSolver.closed_loop takes its gains the same way), stitched on the device into
             info["policy"], a DistributedPolicy; not with `shard` or `ignore_ids`.  policy="wide": the same for ANY team of up to
             256 agents, over the wide front end (multi-word masks; wide=True where k <= 64) and stitch_policy_wide:
-            info["policy"].bits is (S, k, n_words), .rollout runs ProblemBatch.policy_rollout_dec_wide, .advance raises
+            info["policy"].bits is (S, k, n_words), .rollout runs ProblemBatch.policy_rollout_dec_wide, .advance(..., wide=True)
+            ProblemBatch.policy_advance_dec_wide (.advance without it raises)
     returns X_dec (S, T+1, n_x), U_dec (S, T, n_u), J_full (S,), info (clusters as bit masks, counts) -- NumPy arrays, or
     device tensors with device_out=True; with `shard` the unstitched (front end, solved slices) pair instead.
 
     Teams of 64 < k <= 256 agents are served too (multi-word masks, the full-team rollout ProblemBatch.rollout_wide for J_full):
     info["cluster_bits"] is then (S, k, ceil(k / 64)) -- word w, bit b = agent 64 w + b -- instead of (S, k).  Every cluster still
     has at most 64 agents and lies within the solver's own limits.  The closed-loop rollout of such a team: policy="wide".  Not
-    built for such teams: policy=True and shard= (each a ValueError before any device work), the receding-horizon advance of a
-    wide policy, fp32.
+    built for such teams: policy=True and shard= (each a ValueError before any device work), fp32.
     """
     from .sharding import shard_bounds
     if policy and (shard is not None or ignore_ids):

@@ -303,7 +303,7 @@ def solve_rhc_scenarios(problem, x0, N, radius, xf=None, U0=None, centralized=Fa
 
 def solve_rhc_closed_loop(problem, x0, N, radius=None, xf=None, U0=None, centralized=True, feedback=True, W=None, u_lim=None,
                           policy_mu=0.0, n_d=2, step_size=1, dist_converge=None, J_converge=None, max_steps=None, window=None,
-                          large=False, team=False, **kwargs):
+                          large=False, team=False, wide=False, **kwargs):
     """The receding-horizon loop on a REAL plant, for S scenarios in lock step: plan, execute step_size steps of the plan's
     feedback policy under a disturbance and actuator limits, re-plan from where the plant ended up.  solve_rhc and
     solve_rhc_scenarios keep the reference's ideal plant (xi = X[step_size]); here every round is one batched solve over the
@@ -331,8 +331,14 @@ def solve_rhc_closed_loop(problem, x0, N, radius=None, xf=None, U0=None, central
     ProblemBatch.policy_advance_dec_team -- DistributedPolicy.advance(..., team=True) with feedback, the stitched plan open loop
     without --, whose arithmetic is policy_rollout_dec_team's.  A problem of n_x <= 60 and k <= 20 takes the route above
     whatever `team` says.  It is opt-in: without it a larger distributed problem is refused as before.
-    Not built: teams of more than 64 agents, fp32, shard=, ignore_ids.  Device problems only."""
+    wide=True serves the DISTRIBUTED loop (centralized=False) of any lowerable team of 1 .. 256 agents on the wide entries,
+    whatever its size: every round is solve_scenarios_distributed(policy="wide" if feedback else False, ...) and one launch of
+    ProblemBatch.policy_advance_dec_wide -- DistributedPolicy.advance(..., wide=True) with feedback, the stitched plan open loop
+    without --, and the final state's terminal cost is ProblemBatch.cost_wide.  It is opt-in too: without it every refusal is
+    as before, a team of more than 64 agents included.
+    Not built: fp32, shard=, ignore_ids; the wide route as a default.  Device problems only."""
     import torch
+    from . import _lib
     from .batch import ROUTES, ProblemBatch, route_refusal, route_serves
     from .device import to_dev
     from .dispatch import device_constants
@@ -346,13 +352,23 @@ def solve_rhc_closed_loop(problem, x0, N, radius=None, xf=None, U0=None, central
     n_x, n_u = problem.dynamics.n_x, problem.dynamics.n_u
     k = problem.n_agents      # (lowerable: one cost and one (n_s, n_c) per agent)
     n_s, n_c = n_x // k, n_u // k
-    small = route_serves("small", k, n_s, n_c)      # the routes and their limits: batch.ROUTES
-    large = bool(large) and not small
+    if wide:      # the wide entries, whatever the size: none of the routes below
+        if centralized:
+            raise ValueError("solve_rhc_closed_loop: wide=True is the distributed loop (centralized=False) of a team of up to "
+                             f"{_lib.MAX_TEAM} agents")
+        if k > _lib.MAX_TEAM:
+            raise ValueError(f"solve_rhc_closed_loop: wide=True serves teams of up to {_lib.MAX_TEAM} agents (this one has {k})")
+        if n_s == 5 and k > ROUTES["team"]["max_k_of_ns"][5]:
+            raise ValueError(f"solve_rhc_closed_loop: wide=True serves the five-state family up to 12 agents, this one has k = {k}")
+        if kwargs.get("ignore_ids") or kwargs.get("shard") is not None:
+            raise ValueError("solve_rhc_closed_loop: wide=True serves neither shard= nor ignore_ids")
+    small = not wide and route_serves("small", k, n_s, n_c)      # the routes and their limits: batch.ROUTES
+    large = bool(large) and not small and not wide
     if team and centralized:
         raise ValueError("solve_rhc_closed_loop: team=True is the distributed loop (centralized=False); a centralized problem of "
                          "60 < n_x <= 240 is served by large=True")
-    team = bool(team) and not large and not small
-    if not (small or large or team):
+    team = bool(team) and not large and not small and not wide
+    if not (small or large or team or wide):
         raise ValueError(f"solve_rhc_closed_loop serves problems up to n_x = 60, this one has n_x = {n_x} "
                          "(large=True serves a centralized problem of up to n_x = 240, team=True the distributed loop of a team "
                          "of up to 64 agents)")
@@ -430,13 +446,13 @@ def solve_rhc_closed_loop(problem, x0, N, radius=None, xf=None, U0=None, central
         else:
             Xin = state["x_cur"][ia][:, None, :] if first else state["X_next"][ia]
             Xa, Ua, Ja, info = solve_scenarios_distributed(problem, Xin, state["U_next"][ia], radius, xf=xf_d[ia], window=window,
-                                                           device_out=True, desc=d, policy=bool(feedback), policy_mu=float(policy_mu),
-                                                           **solve_kw)
+                                                           device_out=True, desc=d, policy_mu=float(policy_mu),
+                                                           policy="wide" if wide and feedback else bool(feedback), **solve_kw)
             if feedback:
-                info["policy"].advance(h, state, scen=scen, W=W_d, u_lim=lim_d, n_d=n_d, team=team)
+                info["policy"].advance(h, state, scen=scen, W=W_d, u_lim=lim_d, n_d=n_d, team=team, wide=wide)
             else:
                 pb = batch(ia)
-                advance = pb.policy_advance_dec_team if team else pb.policy_advance_dec
+                advance = pb.policy_advance_dec_wide if wide else pb.policy_advance_dec_team if team else pb.policy_advance_dec
                 advance(Xa, Ua, None, None, h, state, scen=scen, W=W_d, u_lim=lim_d, n_d=n_d)
             J[ia] = Ja
         first = False
@@ -446,7 +462,7 @@ def solve_rhc_closed_loop(problem, x0, N, radius=None, xf=None, U0=None, central
         active = active[go & room]
     n_done = state["n_done"].cpu().numpy()
     X_exec, U_exec = state["X_exec"].cpu().numpy(), state["U_exec"].cpu().numpy()
-    J_term = full.cost(state["x_cur"][:, None, :], torch.zeros((S, 1, n_u), dtype=torch.float64, device=dev), terminal=True)[:, 0]
+    J_term = (full.cost_wide if wide else full.cost)(state["x_cur"][:, None, :], torch.zeros((S, 1, n_u), dtype=torch.float64, device=dev), terminal=True)[:, 0]
     return dict(X=[X_exec[s, :n_done[s] + 1].copy() for s in range(S)], U=[U_exec[s, :n_done[s]].copy() for s in range(S)],
                 J=(state["J_exec"] + J_term).cpu().numpy(), min_sep=state["min_sep"].cpu().numpy(),
                 goal_dist=state["dist_left"].cpu().numpy(), converged=converged, n_rounds=n_rounds)

@@ -3,7 +3,7 @@
  * The closed-loop ROLLOUT of a distributed solution for teams of MORE than 64 agents: the stitch of the sub-problems' gains and
  * the rollout itself, over the multi-word neighbourhood masks of dpilqr_swarm.h.  Additive: DPILQR_ABI_VERSION is unchanged.
  * Conventions (device pointers, fp64, row-major, `stream`, error codes): dpilqr_hip.h.
- * Not built for such teams: the receding-horizon advance (dpilqr_policy_advance_dec_team ends at 64 agents) and fp32.
+ * The receding-horizon advance of such teams: dpilqr_swarm_advance.h.  Not built for such teams: fp32.
  */
 #ifndef DPILQR_SWARM_POLICY_H
 #define DPILQR_SWARM_POLICY_H
