@@ -274,7 +274,7 @@ int32_t launch_policy_rollout_dec(const dpilqr_batch_desc& D, const PolicyRollou
 // gains read straight from global memory (policy_dec_team.hpp); enqueue only
 int32_t launch_policy_rollout_dec_team(const dpilqr_batch_desc& D, const PolicyRolloutArgs& a, hipStream_t st);
 // tu_policy_dec_wide.hip: the same closed loop for a team of up to 256 agents, the masks nbr_bits[B][k][n_words] of
-// n_words = ceil(k / 64) words, a neighbourhood of at most 64 members (policy_dec_wide.hpp); enqueue only
+// n_words = ceil(k / 64) words, a neighbourhood of at most 64 members (policy_dec_team.hpp at four mask words); enqueue only
 int32_t launch_policy_rollout_dec_wide(const dpilqr_batch_desc& D, const PolicyRolloutArgs& a, int32_t n_words, hipStream_t st);
 // tu_policy_large.hip: the dense rollout on the large route, K[t] dx on the matrix pipe (policy_large.hpp); enqueue only
 int32_t launch_policy_rollout_large(const dpilqr_batch_desc& D, const PolicyRolloutArgs& a, hipStream_t st);
@@ -285,7 +285,8 @@ int32_t launch_policy_advance(const dpilqr_batch_desc& D, const PolicyAdvanceArg
 // any n_x, a thread per (item, agent), the team rollout's arithmetic (policy_advance_dec_team.hpp); Kc null: open loop; enqueue only
 int32_t launch_policy_advance_dec_team(const dpilqr_batch_desc& D, const PolicyAdvanceArgs& a, hipStream_t st);
 // tu_policy_advance_dec_wide.hip: the same step for a team of up to 256 agents, the masks nbr_bits[B][k][n_words] of
-// n_words = ceil(k / 64) words, a neighbourhood of at most 64 members (policy_advance_dec_wide.hpp); Kc null: open loop; enqueue only
+// n_words = ceil(k / 64) words, a neighbourhood of at most 64 members (policy_advance_dec_team.hpp at four mask words); Kc null:
+// open loop; enqueue only
 int32_t launch_policy_advance_dec_wide(const dpilqr_batch_desc& D, const PolicyAdvanceArgs& a, int32_t n_words, hipStream_t st);
 // tu_policy_advance_large.hip: the advance on the large route, dense gains, one workgroup per item, K[i] dx on the matrix pipe
 // (policy_advance_large.hpp); enqueue only

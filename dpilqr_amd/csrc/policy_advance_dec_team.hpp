@@ -1,6 +1,7 @@
 // policy_advance_dec_team.hpp -- the step between two solves of a receding-horizon loop under a DISTRIBUTED solution's policy, for a
-// whole TEAM of up to 64 agents at any n_x: dpilqr_policy_advance_dec's semantics (include/dpilqr_policy.h, policy_advance.hpp),
-// statement for statement, with k_policy_rollout_dec_team's arithmetic (policy_dec_team.hpp):
+// whole TEAM at any n_x -- up to 64 agents behind one mask word (NW = 1, dpilqr_policy_advance_dec_team), up to 256 behind
+// ceil(k / 64) words (NW = 4, dpilqr_policy_advance_dec_wide): dpilqr_policy_advance_dec's semantics (include/dpilqr_policy.h,
+// policy_advance.hpp), statement for statement, with k_policy_rollout_dec_team's arithmetic (policy_dec_team.hpp):
 //     u_i = clamp( U_ff[j][i] + Kc_i[j][i] (x_{C_i} - X[j][i]_{C_i}) )      x <- step(x, u_i)   [+ W[s][g + i]]
 // The step, the cost terms and the product are the shared device functions -- policy_block, integrate_rt, ref_cost, pair_cost,
 // pair_dist2, sum_in_order are called, not restated -- so the executed prefix equals k_policy_rollout_dec_team's bit for bit, and
@@ -21,6 +22,22 @@
 //               lowest kc_max members among the low k bits are kept when the mask is read, so no address depends on a mask's
 //               value beyond row a of the item's own Kc[j][i] image and the item's own dx rows.  Kc == nullptr: the masks are
 //               not read, the sum is zero.
+//   NW          ONE text over the number of mask words a lane keeps, as in policy_dec_team.hpp: bits [B][k][n_words], n_words =
+//               ceil(k / 64) <= NW, word w, bit b = agent 64 w + b.  Lane (slot, a) reads its n_words words once and keeps, word
+//               by word and lowest bit first, only the lowest kc_max <= 64 members among the low k bits (words at and past
+//               n_words are zero); each step walks the words in that order, block p of the lane's compact rows belongs to its
+//               p-th member (p < kc_max, member < k).  An agent's work per step is what it is in a team of 64 -- only the pairs
+//               grow, up to 128 per lane and step at k = 256, and ipw falls to 3 items per workgroup at k = 65 .. 85, 2 at
+//               86 .. 128, 1 above.  At NW = 1 the read is the single-word form under `if constexpr` and the instantiation
+//               keeps the instructions, registers and LDS of the one-word kernel this header used to hold; with n_words = 1
+//               and k <= 64 the NW = 4 instantiation gives all nine state fields bit for bit
+//               (profiles/policy_dec_words_refactor.txt).
+//               The NW truncated words are held in REGISTERS, as the rollout holds them.  At (12, 4) and NW = 1 the kernel
+//               sits near the register budget of a 256-thread workgroup (512 per lane), so for NW = 4 the alternative -- the
+//               words in LDS, lane tid's word w at w * 256 + tid, 8 KB more -- was built too and both code objects were read
+//               (scripts/kernel_resources.py; profiles/policy_advance_dec_wide_checks.txt has the table): in registers the
+//               twelve-state instantiation takes 360 + 104 registers, 0 spilled, no scratch, 41984 B LDS; in LDS 352 + 96 and
+//               50176 B.  Neither form spills in any family, so the registers are kept and the LDS is the same at both NW.
 //   exchange    SINGLE buffers behind two barriers per step (policy_dec_team.hpp): dx at stride NS | 1, positions at stride 3.
 //               Every loop whose trip count feeds a barrier runs to the uniform h: an item near its capacity executes he < h
 //               steps and its lanes idle through the rest.
@@ -39,24 +56,24 @@
 //               the source index clamped, U_next zero beyond the plan.  U_next / X_next must not alias the plan.
 // Static LDS: 256 (NS | 1) + 256 x 3 + 3 x 256 doubles (stage-cost terms, separations, executed costs), 256 ints (n_dims) and
 // 2 x 256 ints (he, scenario per slot; ipw = 256 at k = 1): 41 KB at twelve states (41984 B), 21 KB at three (21504 B) -- the
-// team rollout's 35 KB plus the advance's bookkeeping.  At 256 + 98 registers per lane one workgroup is resident per CU, so LDS
-// does not bound the occupancy.
+// team rollout's 35 KB plus the advance's bookkeeping, at either NW.  At 256 + 98 registers per lane (NW = 1; 360 + 104 at NW = 4)
+// one workgroup is resident per CU, so LDS does not bound the occupancy.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "policy_dec_team.hpp"      // kPolicyTeamThreads, kPolicyTeamAgents; policy.hpp: pair_dist2, policy_block
+#include "policy_dec_team.hpp"      // kPolicyTeamThreads, kPolicyTeamAgents, kPolicyWide*; policy.hpp: pair_dist2, policy_block
 
 namespace dpilqr {
 
-// X [B][T+1][n_x]: X_dec; U [B][T][n_u]: U_ff; K: Kc [B][T][k][NC][kc_max * NS] or null (open loop); bits [B][k]
+// X [B][T+1][n_x]: X_dec; U [B][T][n_u]: U_ff; K: Kc [B][T][k][NC][kc_max * NS] or null (open loop); bits [B][k][n_words]
 // the loop's state, by scenario (include/dpilqr_policy.h, dpilqr_policy_advance)
-template <int NS, int NC>
+template <int NS, int NC, int NW>
 __global__ __launch_bounds__(kPolicyTeamThreads) void k_policy_advance_dec_team(dpilqr_batch_desc D, const double* __restrict__ X,
-        const double* __restrict__ U, const double* __restrict__ K, int kc_max, const unsigned long long* __restrict__ bits, int h,
-        const int* __restrict__ scen, int n_scen, int L, int n_d, const double* __restrict__ W, const double* __restrict__ u_lim,
-        double* __restrict__ x_cur, int* __restrict__ n_done, double* __restrict__ X_exec, double* __restrict__ U_exec,
-        double* __restrict__ J_exec, double* __restrict__ min_sep, double* __restrict__ dist_left, double* __restrict__ U_next,
-        double* __restrict__ X_next) {
+        const double* __restrict__ U, const double* __restrict__ K, int kc_max, const unsigned long long* __restrict__ bits,
+        int n_words, int h, const int* __restrict__ scen, int n_scen, int L, int n_d, const double* __restrict__ W,
+        const double* __restrict__ u_lim, double* __restrict__ x_cur, int* __restrict__ n_done, double* __restrict__ X_exec,
+        double* __restrict__ U_exec, double* __restrict__ J_exec, double* __restrict__ min_sep, double* __restrict__ dist_left,
+        double* __restrict__ U_next, double* __restrict__ X_next) {
     constexpr int nth = kPolicyTeamThreads, AS = NS | 1;
     constexpr int PD = 3;      // coordinates a pair can ask for (n_dims <= 3 <= NS)
     __shared__ double s_dx[nth * AS];       // lane tid's dx at tid * AS
@@ -109,14 +126,27 @@ __global__ __launch_bounds__(kPolicyTeamThreads) void k_policy_advance_dec_team(
     double* Xe = X_exec + ((int64_t)s * (L + 1) + g) * n + a * NS;
     double* Ue = U_exec + ((int64_t)s * L + g) * m + a * NC;
 
-    // the mask, read once per lane: only its lowest kc_max members among the low k bits are kept
-    unsigned long long mask = 0ull;
+    // the mask, read once per lane: only its lowest kc_max members among the low k bits are kept, counted across the words
+    unsigned long long mask[NW];
+#pragma unroll
+    for (int w = 0; w < NW; ++w) mask[w] = 0ull;
     double x[NS];
     if (active) {
         if (gains) {
-            unsigned long long rem = bits[(int64_t)j * k + a];
-            if (k < 64) rem &= (1ull << k) - 1ull;
-            for (int p = 0; p < kc_max && rem != 0ull; ++p, rem &= rem - 1ull) mask |= rem & (0ull - rem);
+            if constexpr (NW == 1) {
+                unsigned long long rem = bits[(int64_t)j * k + a];
+                if (k < 64) rem &= (1ull << k) - 1ull;
+                for (int p = 0; p < kc_max && rem != 0ull; ++p, rem &= rem - 1ull) mask[0] |= rem & (0ull - rem);
+            } else {
+                int left = kc_max;
+#pragma unroll
+                for (int w = 0; w < NW; ++w) {
+                    const int hi = k - 64 * w;      // bits of this word below k
+                    unsigned long long rem = (w < n_words && hi > 0) ? bits[((int64_t)j * k + a) * n_words + w] : 0ull;
+                    if (hi < 64) rem &= (1ull << (hi > 0 ? hi : 0)) - 1ull;
+                    for (; left > 0 && rem != 0ull; --left, rem &= rem - 1ull) mask[w] |= rem & (0ull - rem);
+                }
+            }
         }
 #pragma unroll
         for (int i = 0; i < NS; ++i) x[i] = x_cur[(int64_t)s * n + a * NS + i];
@@ -161,8 +191,10 @@ __global__ __launch_bounds__(kPolicyTeamThreads) void k_policy_advance_dec_team(
             for (int c = 0; c < NC; ++c) sum[c] = 0.0;
             const double* krow = Kj + (int64_t)i * m * kw;
             int pos = 0;
-            for (unsigned long long rem = mask; rem != 0ull; rem &= rem - 1ull, ++pos)
-                policy_block<NS, NC>(sum, krow, dxs, pos, __ffsll(rem) - 1, 1, kw, AS);      // (rs = 1, row stride kw: global memory)
+#pragma unroll
+            for (int w = 0; w < NW; ++w)      // word by word, lowest bit first: the members in ascending order
+                for (unsigned long long rem = mask[w]; rem != 0ull; rem &= rem - 1ull, ++pos)
+                    policy_block<NS, NC>(sum, krow, dxs, pos, 64 * w + __ffsll(rem) - 1, 1, kw, AS);      // (rs = 1, row stride kw: global memory)
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
                 double v = Uj[(int64_t)i * m + c] + sum[c];

@@ -1,5 +1,6 @@
-// policy_dec_team.hpp -- the closed loop of a DISTRIBUTED solution for a whole TEAM of up to 64 agents: dpilqr_policy_rollout_dec's
-// definition (include/dpilqr_policy.h, policy_dec.hpp), unchanged,
+// policy_dec_team.hpp -- the closed loop of a DISTRIBUTED solution for a whole TEAM: up to 64 agents behind one mask word
+// (NW = 1, dpilqr_policy_rollout_dec_team), up to 256 behind ceil(k / 64) words (NW = 4, dpilqr_policy_rollout_dec_wide).
+// dpilqr_policy_rollout_dec's definition (include/dpilqr_policy.h, policy_dec.hpp), unchanged,
 //     u_i(t) = U_ff_i[t] + Kc_i[t] (x_{C_i}(t) - X_dec[t]_{C_i})   [clamped to u_lim]      x_{t+1} = step(x_t, u_t)   [+ W[t]]
 // where the full problem is beyond any centralised kernel (n_x = 256 at 64 double integrators) but the per-agent work is still
 // n_c x kc_i n_s multiply-adds per step.  The step, the cost terms and the product are the device functions the other rollouts
@@ -19,6 +20,18 @@
 //               made 32 items slower (4.68 against 3.48 ms): that variant was not kept (profiles/policy_dec_team.txt).
 //               Only the lowest kc_max members among the low k bits are kept when the mask is read, so no address
 //               depends on a mask's value beyond row a of the Kc[b][t] image and the sample's own dx row.
+//   NW          the kernel is ONE text over the number of mask words a lane keeps, a template parameter: bits [B][k][n_words],
+//               n_words = ceil(k / 64) <= NW, word w, bit b = agent 64 w + b (frontend_wide.hpp).  A neighbourhood still has at
+//               most kc_max <= 64 members (a sub-problem's limit), so an agent's work per step is what it is in a team of 64 --
+//               only the pairs grow, up to 128 per thread and step at k = 256, and G = floor(256 / k) falls to 3 samples per
+//               workgroup at k = 65 .. 85, 2 at 86 .. 128, 1 above.  Lane (sl, a) reads its n_words words once and keeps, word
+//               by word and lowest bit first, only the lowest kc_max members among the low k bits: NW truncated words in
+//               registers (words at and past n_words are zero).  Each step walks them in that order; block p of the agent's
+//               compact rows belongs to its p-th member (p < kc_max, member < k).  At NW = 1 the read is the single-word form
+//               under `if constexpr`, the walk's word loop has one trip, and the instantiation keeps the instructions,
+//               registers and LDS of the one-word kernel this header used to hold (profiles/policy_dec_words_refactor.txt);
+//               with n_words = 1 and k <= 64 the NW = 4 instantiation gives all five results bit for bit (same device
+//               functions, same order).
 //   exchange    each step a thread publishes dx_a = x_a - X[t]_a (stride NS | 1, odd) and its position (three coordinates) in
 //               LDS.  SINGLE buffers behind a second barrier instead of policy.hpp's parities: two parities of 256 x 13 doubles
 //               plus the positions pass 64 KB at twelve states, and a barrier is small change beside a step's gain reads.
@@ -33,7 +46,7 @@
 //               and there is no floating-point atomic and NO wavefront-wide operation: samples straddle wavefronts whenever k
 //               does not divide 64.  min_sep: every thread keeps the smallest squared distance of its own pairs, lane a = 0 takes
 //               the minimum of the sample's k values at the end.
-// Static LDS: 256 (NS | 1) + 256 x 3 + 256 doubles and 64 ints -- 35 KB at twelve states.
+// Static LDS: 256 (NS | 1) + 256 x 3 + 256 doubles and 64 NW ints (n_dims) -- 35 KB at twelve states and NW = 1, 36 KB at NW = 4.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -43,21 +56,24 @@ namespace dpilqr {
 
 constexpr int kPolicyTeamThreads = 256;
 constexpr int kPolicyTeamAgents = 64;      // one mask word
+constexpr int kPolicyWideWords = 4;
+constexpr int kPolicyWideAgents = 64 * kPolicyWideWords;     // one thread per agent of a sample
+constexpr int kPolicyWideMembers = 64;     // a neighbourhood is a sub-problem: at most 64 agents
 
-// X [B][T+1][n_x]: X_dec; U [B][T][n_u]: U_ff; K: Kc [B][T][k][NC][kc_max * NS]; bits [B][k]
+// X [B][T+1][n_x]: X_dec; U [B][T][n_u]: U_ff; K: Kc [B][T][k][NC][kc_max * NS]; bits [B][k][n_words]
 // Xs [B][S][T+1][n_x], Us [B][S][T][n_u] (either may be null); J, min_sep [B][S]; goal_dist [B][S][k] (the last two may be null)
-template <int NS, int NC>
+template <int NS, int NC, int NW>
 __global__ __launch_bounds__(kPolicyTeamThreads) void k_policy_rollout_dec_team(dpilqr_batch_desc D, const double* __restrict__ X,
         const double* __restrict__ U, const double* __restrict__ K, int kc_max, const unsigned long long* __restrict__ bits,
-        int S, int chunks, const double* __restrict__ x0s, const double* __restrict__ W, const double* __restrict__ u_lim,
-        double* __restrict__ Xs, double* __restrict__ Us, double* __restrict__ J_out, double* __restrict__ min_sep,
-        double* __restrict__ goal_dist) {
+        int n_words, int S, int chunks, const double* __restrict__ x0s, const double* __restrict__ W,
+        const double* __restrict__ u_lim, double* __restrict__ Xs, double* __restrict__ Us, double* __restrict__ J_out,
+        double* __restrict__ min_sep, double* __restrict__ goal_dist) {
     constexpr int nth = kPolicyTeamThreads, AS = NS | 1;
     constexpr int PD = 3;      // coordinates a pair can ask for (n_dims <= 3 <= NS)
     __shared__ double s_dx[nth * AS];       // lane tid's dx at tid * AS
     __shared__ double s_pos[nth * PD];      // lane tid's position at tid * 3: an odd stride
     __shared__ double s_term[nth];          // lane tid's share of its sample's stage cost
-    __shared__ int32_t s_nd[kPolicyTeamAgents];
+    __shared__ int32_t s_nd[64 * NW];
     const int tid = (int)threadIdx.x;
     const int b = (int)blockIdx.x / chunks, chunk = (int)blockIdx.x - b * chunks;
     const int k = D.k, T = D.T, n = k * NS, m = k * NC, kw = kc_max * NS;
@@ -84,13 +100,26 @@ __global__ __launch_bounds__(kPolicyTeamThreads) void k_policy_rollout_dec_team(
     double* Uw = (Us && active) ? Us + smp * T * m + a * NC : nullptr;
     const bool clamp = u_lim != nullptr, noisy = W != nullptr;      // uniform: no per-lane pointer test inside the loop
 
-    // the mask, read once per lane: only its lowest kc_max members among the low k bits are kept
-    unsigned long long mask = 0ull;
+    // the mask, read once per lane: only its lowest kc_max members among the low k bits are kept, counted across the words
+    unsigned long long mask[NW];
+#pragma unroll
+    for (int w = 0; w < NW; ++w) mask[w] = 0ull;
     double x[NS];
     if (active) {
-        unsigned long long rem = bits[(int64_t)b * k + a];
-        if (k < 64) rem &= (1ull << k) - 1ull;
-        for (int p = 0; p < kc_max && rem != 0ull; ++p, rem &= rem - 1ull) mask |= rem & (0ull - rem);
+        if constexpr (NW == 1) {
+            unsigned long long rem = bits[(int64_t)b * k + a];
+            if (k < 64) rem &= (1ull << k) - 1ull;
+            for (int p = 0; p < kc_max && rem != 0ull; ++p, rem &= rem - 1ull) mask[0] |= rem & (0ull - rem);
+        } else {
+            int left = kc_max;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) {
+                const int hi = k - 64 * w;      // bits of this word below k
+                unsigned long long rem = (w < n_words && hi > 0) ? bits[((int64_t)b * k + a) * n_words + w] : 0ull;
+                if (hi < 64) rem &= (1ull << (hi > 0 ? hi : 0)) - 1ull;
+                for (; left > 0 && rem != 0ull; --left, rem &= rem - 1ull) mask[w] |= rem & (0ull - rem);
+            }
+        }
 #pragma unroll
         for (int i = 0; i < NS; ++i) {
             x[i] = x0s[smp * n + a * NS + i];
@@ -132,8 +161,10 @@ __global__ __launch_bounds__(kPolicyTeamThreads) void k_policy_rollout_dec_team(
             for (int c = 0; c < NC; ++c) sum[c] = 0.0;
             const double* krow = Kb + (int64_t)t * m * kw;
             int pos = 0;
-            for (unsigned long long rem = mask; rem != 0ull; rem &= rem - 1ull, ++pos)
-                policy_block<NS, NC>(sum, krow, dxs, pos, __ffsll(rem) - 1, 1, kw, AS);      // (rs = 1, row stride kw: global memory)
+#pragma unroll
+            for (int w = 0; w < NW; ++w)      // word by word, lowest bit first: the members in ascending order
+                for (unsigned long long rem = mask[w]; rem != 0ull; rem &= rem - 1ull, ++pos)
+                    policy_block<NS, NC>(sum, krow, dxs, pos, 64 * w + __ffsll(rem) - 1, 1, kw, AS);      // (rs = 1, row stride kw: global memory)
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
                 double v = Ub[(int64_t)t * m + c] + sum[c];

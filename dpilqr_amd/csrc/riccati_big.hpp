@@ -484,8 +484,8 @@ __global__ __launch_bounds__(kBigThreads) void k_riccati_big(dpilqr_batch_desc D
             dout[gslot * (int64_t)T * m] = (R)__builtin_nan("");
         }
     };
-    // (the team also shares S1 where S1 is the matrix-pipe form -- twelve-state fp64, config 5; the vector forms of the other
-    // instantiations keep it on the main workgroup: with the helper's copy of them the fp32 twelve-state kernel spilled 40 registers)
+    // (the team also shares S1 in the twelve-state clusters, fp64 and fp32 alike -- config 5, where fp64 has the matrix-pipe form;
+    // the other families keep S1 on the main workgroup)
 #ifdef DPILQR_BIG_TEAM_S1_ALL
     constexpr bool kTeamS1 = true;
 #else

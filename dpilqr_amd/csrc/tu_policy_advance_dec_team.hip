@@ -16,8 +16,8 @@ int32_t launch_policy_advance_dec_team(const dpilqr_batch_desc& D, const PolicyA
     if (blocks > 0x7fffffffLL) return fail(DPILQR_EUNSUPPORTED, "policy_advance_dec_team: %lld workgroups", (long long)blocks);
     if (D.B == 0) return DPILQR_OK;
     DISPATCH_FAMILY_ALL(D.n_s, {
-        hipLaunchKernelGGL((k_policy_advance_dec_team<NS, NC>), dim3((unsigned)blocks), dim3(kPolicyTeamThreads), 0, st, D, a.plan.X, a.plan.U,
-                           a.plan.K, (int)a.plan.kc_max, reinterpret_cast<const unsigned long long*>(a.plan.nbr_bits), (int)a.h, a.scen,
+        hipLaunchKernelGGL((k_policy_advance_dec_team<NS, NC, 1>), dim3((unsigned)blocks), dim3(kPolicyTeamThreads), 0, st, D, a.plan.X, a.plan.U,
+                           a.plan.K, (int)a.plan.kc_max, reinterpret_cast<const unsigned long long*>(a.plan.nbr_bits), 1, (int)a.h, a.scen,
                            (int)a.n_scen, (int)a.L, (int)a.n_d, a.W, a.u_lim, a.x_cur, a.n_done, a.X_exec, a.U_exec, a.J_exec, a.min_sep,
                            a.dist_left, a.U_next, a.X_next);
     })

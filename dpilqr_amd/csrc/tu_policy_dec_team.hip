@@ -16,9 +16,9 @@ int32_t launch_policy_rollout_dec_team(const dpilqr_batch_desc& D, const PolicyR
     if (chunks * D.B > 0x7fffffffLL) return fail(DPILQR_EUNSUPPORTED, "policy_rollout_dec_team: %lld workgroups", (long long)(chunks * D.B));
     if (D.B == 0) return DPILQR_OK;
     DISPATCH_FAMILY_ALL(D.n_s, {
-        hipLaunchKernelGGL((k_policy_rollout_dec_team<NS, NC>), dim3((unsigned)(chunks * D.B)), dim3(kPolicyTeamThreads), 0, st, D, a.plan.X,
+        hipLaunchKernelGGL((k_policy_rollout_dec_team<NS, NC, 1>), dim3((unsigned)(chunks * D.B)), dim3(kPolicyTeamThreads), 0, st, D, a.plan.X,
                            a.plan.U, a.plan.K, (int)a.plan.kc_max, reinterpret_cast<const unsigned long long*>(a.plan.nbr_bits),
-                           (int)a.n_samples, (int)chunks, a.x0s, a.W, a.u_lim, a.Xs, a.Us, a.J, a.min_sep, a.goal_dist);
+                           1, (int)a.n_samples, (int)chunks, a.x0s, a.W, a.u_lim, a.Xs, a.Us, a.J, a.min_sep, a.goal_dist);
     })
     HIP_TRY(hipGetLastError());
     return DPILQR_OK;

@@ -1,9 +1,9 @@
-// tu_policy_dec_wide.hip -- the closed loop of a distributed solution for teams of up to 256 agents (policy_dec_wide.hpp) and its
-// launcher.
+// tu_policy_dec_wide.hip -- the closed loop of a distributed solution for teams of up to 256 agents (policy_dec_team.hpp, four
+// mask words) and its launcher.
 #include <hip/hip_runtime.h>
 
 #include "launch.hpp"
-#include "policy_dec_wide.hpp"
+#include "policy_dec_team.hpp"
 
 namespace dpilqr {
 
@@ -16,12 +16,12 @@ int32_t launch_policy_rollout_dec_wide(const dpilqr_batch_desc& D, const PolicyR
                     a.plan.kc_max, kPolicyWideMembers, kc_lim);
     if (n_words != (D.k + 63) / 64)
         return fail(DPILQR_EINVAL, "policy_rollout_dec_wide: n_words=%d, k=%d agents take ceil(k / 64) = %d words", n_words, D.k, (D.k + 63) / 64);
-    const int spw = kPolicyWideThreads / D.k;                  // samples of one item per workgroup
+    const int spw = kPolicyTeamThreads / D.k;                  // samples of one item per workgroup
     const int64_t chunks = ((int64_t)a.n_samples + spw - 1) / spw;
     if (chunks * D.B > 0x7fffffffLL) return fail(DPILQR_EUNSUPPORTED, "policy_rollout_dec_wide: %lld workgroups", (long long)(chunks * D.B));
     if (D.B == 0) return DPILQR_OK;
     DISPATCH_FAMILY_ALL(D.n_s, {
-        hipLaunchKernelGGL((k_policy_rollout_dec_wide<NS, NC>), dim3((unsigned)(chunks * D.B)), dim3(kPolicyWideThreads), 0, st, D, a.plan.X,
+        hipLaunchKernelGGL((k_policy_rollout_dec_team<NS, NC, kPolicyWideWords>), dim3((unsigned)(chunks * D.B)), dim3(kPolicyTeamThreads), 0, st, D, a.plan.X,
                            a.plan.U, a.plan.K, (int)a.plan.kc_max, reinterpret_cast<const unsigned long long*>(a.plan.nbr_bits),
                            (int)n_words, (int)a.n_samples, (int)chunks, a.x0s, a.W, a.u_lim, a.Xs, a.Us, a.J, a.min_sep, a.goal_dist);
     })

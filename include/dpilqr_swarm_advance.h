@@ -25,7 +25,7 @@
  * all nine state fields equal dpilqr_policy_advance_dec_team's bit for bit.  No floating-point atomics: the same bits whatever the
  * batch or the item's place in it.  One workgroup holds floor(256 / k) ITEMS -- 3 at k = 65 .. 85, 2 at 86 .. 128, 1 above --, a
  * thread per (item, agent) reads its own compact rows straight from global memory; thread a takes the pairs (a, a + dd mod k),
- * dd = 1 .. k / 2 (csrc/policy_advance_dec_wide.hpp).
+ * dd = 1 .. k / 2 (csrc/policy_advance_dec_team.hpp at four mask words).
  * DPILQR_EINVAL: the conditions of dpilqr_policy_advance_dec_team (a NULL pointer; h < 1 or h > T; L < 1; n_d outside 1 .. n_s;
  * n_scen < B; a misaligned pointer; nbr_bits NULL while Kc is given; (n_s, n_c) not a model family); n_words != ceil(k / 64).
  * DPILQR_EUNSUPPORTED, before any launch: k > DPILQR_MAX_TEAM; kc_max outside 1 .. min(k, DPILQR_MAX_AGENTS) (checked whether or

@@ -42,7 +42,7 @@ int32_t dpilqr_dispatch_stitch_policy_wide(int32_t S, int32_t k, int32_t n_s, in
  * k alone, the same bits whatever n_samples, the batch or the item's place in it.  With n_words = 1 and k <= 64 all five results
  * (Xs, Us, J, min_sep, goal_dist) equal dpilqr_policy_rollout_dec_team's bit for bit.
  * A thread per (sample, agent), floor(256 / k) samples of one item per workgroup, the compact rows read straight from global
- * memory (csrc/policy_dec_wide.hpp).
+ * memory (csrc/policy_dec_team.hpp at four mask words).
  * DPILQR_EINVAL: the NULL, alignment and n_samples < 1 conditions of dpilqr_policy_rollout_dec_team; n_words != ceil(k / 64);
  * (n_s, n_c) not a model family.  DPILQR_EUNSUPPORTED, before any launch: k > DPILQR_MAX_TEAM; kc_max outside
  * 1 .. min(k, DPILQR_MAX_AGENTS); more than 12 agents of the five-state family (dpilqr_rollout's limit); more than 2^31 - 1

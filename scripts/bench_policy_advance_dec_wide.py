@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""Launch time of the wide receding-horizon advance (dpilqr_policy_advance_dec_wide, csrc/policy_advance_dec_wide.hpp) beside what
-the same result cost before it existed and beside the solve of the same round.  Nothing is asserted: nobody has measured this
+"""Launch time of the wide receding-horizon advance (dpilqr_policy_advance_dec_wide, csrc/policy_advance_dec_team.hpp at four
+mask words) beside what the same result cost before it existed and beside the solve of the same round.  Nothing is asserted: nobody has measured this
 kernel before, and no time is a pass criterion.
 
 Workloads: DoubleIntDynamics4D teams of k = 65, 128 and 256 agents, T = 50, under a disturbance and control limits, neighbourhoods

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Launch time of the closed-loop rollout for teams of up to 256 agents (dpilqr_policy_rollout_dec_wide,
-csrc/policy_dec_wide.hpp).  Nothing is asserted and no target is set: nobody has measured this kernel before, and the open-loop
+csrc/policy_dec_team.hpp at four mask words).  Nothing is asserted and no target is set: nobody has measured this kernel before, and the open-loop
 figure beside each row is only the yardstick the numbers are read against.
 
 Workloads: DoubleIntDynamics4D teams of k = 65, 128 and 256 agents (n_x = 260 .. 1024), T = 50, 64 samples per item, 1 and 32

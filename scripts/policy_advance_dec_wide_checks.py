@@ -20,11 +20,14 @@ sys.path.insert(0, str(ROOT / "scripts"))
 ROW = "%-36s vgpr %3d agpr %3d sgpr %3d spill v %d scratch %d B  static lds %5d B  wg %d"
 
 
-def resource_rows(so_path, needle):
+def resource_rows(so_path, stem):
+    """The rows of the five kernels recorded as `stem<NS, NC>`, under today's names (tests/policy_dec_wide_cases.py: kernel_names)."""
     import kernel_resources
+    from tests.policy_dec_wide_cases import kernel_names
+    names = kernel_names(stem)
     return [ROW % (r["demangled"], r["vgpr_count"], r["agpr_count"], r["sgpr_count"], r["vgpr_spill_count"], r["private_segment_fixed_size"],
                    r["group_segment_fixed_size"], r["max_flat_workgroup_size"])
-            for r in kernel_resources.resources(so_path) if needle in r["demangled"]]
+            for r in kernel_resources.resources(so_path) if r["demangled"] in names]
 
 
 def main():
@@ -101,11 +104,11 @@ def main():
     import kernel_resources
     so = ROOT / "dpilqr_amd" / "libdpilqr_hip.so"
     if (kernel_resources.LLVM / "llvm-readelf").exists() and so.exists():
-        lines += ["", "%d. kernel resources of the built library (scripts/kernel_resources.py), no unit flag: the new kernel, and the two it restates "
+        lines += ["", "%d. kernel resources of the built library (scripts/kernel_resources.py), no unit flag: the wide advance, then the team advance and the wide rollout "
                   "(unchanged against profiles/policy_advance_dec_team_checks.txt and profiles/policy_dec_wide_checks.txt)" % section]
         section += 1
-        for needle in ("k_policy_advance_dec_wide", "k_policy_advance_dec_team", "k_policy_rollout_dec_wide"):
-            lines += resource_rows(so, needle)
+        for stem in ("k_policy_advance_dec_wide", "k_policy_advance_dec_team", "k_policy_rollout_dec_wide"):
+            lines += resource_rows(so, stem)
     if a.masks_in_lds:
         lines += ["", "%d. the mask words: registers or LDS.  Shipped: the four truncated words of a lane in REGISTERS (the table above: 0 spilled, 0 B "
                   "scratch in all five instantiations, the team advance's LDS).  The alternative -- the words in LDS, lane tid's word w at w * 256 + tid, "
@@ -115,7 +118,7 @@ def main():
         lines.append("Neither form spills; the registers were the first choice and leave the LDS as it is, so they were taken.  Not measured: "
                      "the two forms' run time against one another.")
     if a.mutants:
-        lines += ["", "%d. mutants: arithmetic-only changes of k_policy_advance_dec_wide, each built apart from the shipped library, loaded in its place and "
+        lines += ["", "%d. mutants: arithmetic-only changes of the wide advance (k_policy_advance_dec_team at four mask words), each built apart from the shipped library, loaded in its place and "
                   "run ONCE against tests/test_gpu_policy_advance_dec_wide.py (no mutant removes a barrier, a bounds test or an activity test; every "
                   "address stays inside the caller's buffers)" % section]
         lines += Path(a.mutants).read_text().rstrip().splitlines()

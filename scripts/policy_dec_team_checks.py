@@ -63,10 +63,11 @@ def main():
                 lines.append("%-26s %-5s same bits: X %s U %s goal_dist %s J %s min_sep %s; J %.2e min_sep %.2e"
                              % (case.id, v, bits["X"], bits["U"], bits["goal_dist"], bits["J"], bits["min_sep"], eJ, eS))
     import kernel_resources
+    from tests.policy_dec_wide_cases import kernel_names
     if (kernel_resources.LLVM / "llvm-readelf").exists() and (ROOT / "dpilqr_amd" / "libdpilqr_hip.so").exists():
         lines += ["", "%d. kernel resources of the built library (scripts/kernel_resources.py), no unit flag" % (2 if a.cpu_only else 4)]
         for r in kernel_resources.resources():
-            if "k_policy_rollout_dec_team" in r["demangled"]:
+            if r["demangled"] in kernel_names("k_policy_rollout_dec_team"):      # the one-word instantiations
                 lines.append("%-36s vgpr %3d agpr %3d sgpr %3d spill v %d scratch %d B  static lds %5d B  wg %d"
                              % (r["demangled"], r["vgpr_count"], r["agpr_count"], r["sgpr_count"], r["vgpr_spill_count"],
                                 r["private_segment_fixed_size"], r["group_segment_fixed_size"], r["max_flat_workgroup_size"]))

@@ -5,7 +5,7 @@ policy_rollout_dec_team, the kernels' resources in the built library, and MUTANT
 each.  Writes profiles/policy_dec_wide_checks.txt.  Nothing is asserted here: the tests (tests/test_policy_dec_wide_host.py,
 tests/test_gpu_policy_dec_wide.py) hold what this records.
 
-A mutant is one statement of csrc/policy_dec_wide.hpp or csrc/frontend_wide.hpp changed in a copy under build/mutants/, that
+A mutant is one statement of csrc/policy_dec_team.hpp or csrc/frontend_wide.hpp changed in a copy under build/mutants/, that
 copy's translation unit compiled and linked with the current objects of the others into dpilqr_amd/variants/ (git-ignored).
 Every mutant keeps every address inside the arrays the kernel is given (the reason stands beside each below): they compute
 wrong numbers, nothing else.  --build-mutants needs hipcc and no GPU; a run with a GPU then takes each library that is there
@@ -31,17 +31,17 @@ VARIANTS_DIR = ROOT / "dpilqr_amd" / "variants"
 
 # name -> (unit, header, the statement, its replacement, what it does, why it stays inside its arrays)
 MUTANTS = {
-    "words_reversed": ("tu_policy_dec_wide", "policy_dec_wide.hpp",
+    "words_reversed": ("tu_policy_dec_wide", "policy_dec_team.hpp",
                        "for (int w = 0; w < NW; ++w)      // word by word, lowest bit first: the members in ascending order",
                        "for (int w = NW - 1; w >= 0; --w)",
                        "the members of the higher words are walked before those of word 0",
                        "the same members (< k) and the same number of blocks (<= kc_max), in another order"),
-    "word_offset_dropped": ("tu_policy_dec_wide", "policy_dec_wide.hpp",
+    "word_offset_dropped": ("tu_policy_dec_wide", "policy_dec_team.hpp",
                             "pos, 64 * w + __ffsll(rem) - 1, 1, kw, AS);",
                             "pos, __ffsll(rem) - 1, 1, kw, AS);",
                             "a member of word w is taken for agent b instead of 64 w + b",
                             "b < 64 and, in word 0, b < k: a row of the sample's own dx"),
-    "half_offset_by_every_lane": ("tu_policy_dec_wide", "policy_dec_wide.hpp",
+    "half_offset_by_every_lane": ("tu_policy_dec_wide", "policy_dec_team.hpp",
                                   "if (2 * dd == k && a >= dd) break;",
                                   "",
                                   "at even k every lane takes the offset k / 2: those pairs count twice",
@@ -153,10 +153,11 @@ def main():
             lines.append("%-26s k %2d  " % (case.id, case.k) + "  ".join("%s: %s" % (v, ", ".join(keys) if keys else "none") for v, keys in differ.items()))
     import kernel_resources
     if (kernel_resources.LLVM / "llvm-readelf").exists() and (ROOT / "dpilqr_amd" / "libdpilqr_hip.so").exists():
-        lines += ["", "%d. kernel resources of the built library (scripts/kernel_resources.py), no unit flag; the team kernel beside its restatement"
+        lines += ["", "%d. kernel resources of the built library (scripts/kernel_resources.py), no unit flag; the four-word instantiations beside the one-word ones"
                   % (2 if a.cpu_only else 4)]
+        shown = wc.kernel_names("k_policy_rollout_dec_wide") + wc.kernel_names("k_policy_rollout_dec_team")
         for r in kernel_resources.resources():
-            if any(s in r["demangled"] for s in ("k_policy_rollout_dec_wide", "k_policy_rollout_dec_team", "k_stitch_policy")):
+            if r["demangled"] in shown or "k_stitch_policy" in r["demangled"]:
                 lines.append("%-36s vgpr %3d agpr %3d sgpr %3d spill v %d scratch %d B  static lds %5d B  wg %d"
                              % (r["demangled"], r["vgpr_count"], r["agpr_count"], r["sgpr_count"], r["vgpr_spill_count"],
                                 r["private_segment_fixed_size"], r["group_segment_fixed_size"], r["max_flat_workgroup_size"]))

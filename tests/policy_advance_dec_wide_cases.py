@@ -1,6 +1,6 @@
 """Shared by tests/test_policy_advance_dec_wide_host.py, tests/test_gpu_policy_advance_dec_wide.py and
 scripts/policy_advance_dec_wide_checks.py: the receding-horizon advance of a team of up to 256 agents
-(dpilqr_policy_advance_dec_wide, csrc/policy_advance_dec_wide.hpp) on the six cases of tests/policy_dec_wide_cases.py, which are
+(dpilqr_policy_advance_dec_wide, csrc/policy_advance_dec_team.hpp at four mask words) on the six cases of tests/policy_dec_wide_cases.py, which are
 imported and not changed.  Every (item i, sample s) of a case becomes ONE scenario q = i * S + s whose plan is item i's (X, U_ff,
 Kc, words), repeated, as tests/policy_advance_dec_team_cases.py does it for the team advance.  Nothing here touches the GPU.
 

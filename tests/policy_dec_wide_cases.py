@@ -1,6 +1,7 @@
 """Shared by tests/test_gpu_policy_dec_wide.py, tests/test_policy_dec_wide_host.py and scripts/policy_dec_wide_checks.py: the cases
-of the closed-loop rollout for teams of up to 256 agents (dpilqr_policy_rollout_dec_wide, csrc/policy_dec_wide.hpp) and the CPU
-side of their check.  Nothing here touches the GPU.
+of the closed-loop rollout for teams of up to 256 agents (dpilqr_policy_rollout_dec_wide, csrc/policy_dec_team.hpp at four mask
+words) and the CPU side of their check; kernel_name, today's name of a team or wide closed-loop kernel, is shared with the team
+host tests and check scripts too.  Nothing here touches the GPU.
 
 Reused: policy_cases.Case, make_batch, bound_of, difference, MAX_UNCHECKED and the conditions of policy_cases.CaseRef;
 policy_dec_team_cases.separation.  policy_dec_cases.DecCaseRef is NOT reused: its item 0 has a full mask (a wide neighbourhood has
@@ -28,6 +29,8 @@ tests/test_policy_dec_wide_host.py::test_case_conditions.  A six-state case (66 
 with S = 3 and two seeds it moves 0.33 of its samples at sigma 0.6 and 0.44 at 0.7 (0.5 is asked), and leaves 0.11 to 0.22 of
 them without a bound at sigma 0.7 to 0.8 (0.05 is the cap), so it is not among the cases; the six-state instantiation is covered by the n_words = 1 cross-check against policy_rollout_dec_team on
 team-quad6-k21-S13."""
+import re
+
 import numpy as np
 
 from tests import linesearch_cases as lc
@@ -54,6 +57,23 @@ CASES = [
     WideCase("wide-dint4-k256-S2", [0] * 256, 2, 0.3, 0.3, 8, seed=256),
 ]
 IDS = [c.id for c in CASES]
+
+_RECORDED_KERNEL = re.compile(r"k_policy_(rollout|advance)_dec_(team|wide)<(\d+), (\d+)>")
+
+
+def kernel_name(recorded):
+    """Today's demangled name of a team or wide closed-loop kernel, from the name the files under profiles/ recorded it by.  The
+    two widths are one kernel text over the mask word count NW (csrc/policy_dec_team.hpp, csrc/policy_advance_dec_team.hpp):
+    `k_policy_rollout_dec_wide<12, 4>` is `k_policy_rollout_dec_team<12, 4, 4>`, `k_policy_advance_dec_team<4, 2>` is
+    `k_policy_advance_dec_team<4, 2, 1>`."""
+    kind, width, ns, nc = _RECORDED_KERNEL.fullmatch(recorded).groups()
+    return f"k_policy_{kind}_dec_team<{ns}, {nc}, {4 if width == 'wide' else 1}>"
+
+
+def kernel_names(stem):
+    """Today's names of the five instantiations recorded as `stem<NS, NC>` (stem: k_policy_rollout_dec_wide, ...), for the check
+    scripts that list a kernel's rows."""
+    return [kernel_name(f"{stem}<{ns}, {nc}>") for ns, nc in ((3, 2), (4, 2), (5, 2), (6, 3), (12, 4))]
 
 
 def make_members(case):

@@ -1,4 +1,4 @@
-"""The receding-horizon advance of a team of up to 256 agents (dpilqr_policy_advance_dec_wide, csrc/policy_advance_dec_wide.hpp)
+"""The receding-horizon advance of a team of up to 256 agents (dpilqr_policy_advance_dec_wide, csrc/policy_advance_dec_team.hpp at four mask words)
 on the GPU, the cost of a point of such a team (dpilqr_cost_eval_wide), and the distributed loop built on them
 (solve_rhc_closed_loop(centralized=False, wide=True)).
 

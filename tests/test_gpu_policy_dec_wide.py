@@ -1,5 +1,5 @@
 """The closed-loop rollout of a distributed solution for teams of up to 256 agents (dpilqr_policy_rollout_dec_wide,
-csrc/policy_dec_wide.hpp) and the stitch of its gains (dpilqr_dispatch_stitch_policy_wide) on the GPU.
+csrc/policy_dec_team.hpp at four mask words) and the stitch of its gains (dpilqr_dispatch_stitch_policy_wide) on the GPU.
 
   reference   per case of tests/policy_dec_wide_cases.py and variant (plain, W, u_lim), every sample against the CPU reference
               within its own bound bound_of(spread); the kernel gets the compact gains with every unused column NaN; with /

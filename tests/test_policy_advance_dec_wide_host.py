@@ -1,7 +1,7 @@
 """The receding-horizon advance for teams of up to 256 agents, the host side, without a GPU: the two entries of
 include/dpilqr_swarm_advance.h (declared, bound, exported; every refusal before any launch, with fake, aligned device pointers
 that are never dereferenced), the Python layers' refusals before any device work, the pinned tables, the new kernels' resources
-in the built library beside the figures the kernels it restates keep, the conditions that keep the cases of
+in the built library beside the figures the team advance and the wide rollout keep, the conditions that keep the cases of
 tests/policy_advance_dec_wide_cases.py honest on the prefixes the GPU tests execute (from the CPU reference alone), and the
 kernel's member walk in NumPy."""
 import ctypes as C
@@ -394,7 +394,7 @@ def table(lib):
 
 @pytest.mark.parametrize("ns,nc", FAMILIES)
 def test_wide_advance_kernels_keep_every_register(table, ns, nc):
-    r = table[f"k_policy_advance_dec_wide<{ns}, {nc}>"]
+    r = table[wc.kernel_name(f"k_policy_advance_dec_wide<{ns}, {nc}>")]
     assert r["vgpr_spill_count"] == 0 and r["private_segment_fixed_size"] == 0, r
     assert r["max_flat_workgroup_size"] == 256, r
     # static LDS: the team advance's 256 (ns | 1) + 256 * 3 + 3 * 256 doubles and 3 * 256 ints at the least, under 64 KB
@@ -402,8 +402,9 @@ def test_wide_advance_kernels_keep_every_register(table, ns, nc):
 
 
 def test_no_further_wide_advance_kernel_was_built(table):
-    names = sorted(n for n in table if "k_policy_advance_dec_wide" in n)
-    assert names == sorted(f"k_policy_advance_dec_wide<{ns}, {nc}>" for ns, nc in FAMILIES)
+    # one kernel text, two word counts: the five four-word instantiations beside the five one-word ones, and nothing else
+    names = sorted(n for n in table if "k_policy_advance_dec_team" in n or "k_policy_advance_dec_wide" in n)
+    assert names == sorted(wc.kernel_name(f"k_policy_advance_dec_{width}<{ns}, {nc}>") for width in ("team", "wide") for ns, nc in FAMILIES)
 
 
 def _recorded(path):
@@ -413,12 +414,13 @@ def _recorded(path):
 
 
 def test_the_restated_kernels_keep_their_recorded_figures(table):
-    """The team advance and the wide rollout are restated, not shared: registers and LDS are what their checks files record."""
+    """The team advance and the wide rollout -- the one-word advance and the four-word rollout of the shared kernel texts, under
+    the names their checks files recorded them by: registers and LDS are what those files record."""
     team = {n: f for n, f in _recorded("policy_advance_dec_team_checks.txt").items() if n.startswith("k_policy_advance_dec_team<")}
     wide = {n: f for n, f in _recorded("policy_dec_wide_checks.txt").items() if n.startswith("k_policy_rollout_dec_wide<")}
     assert len(team) == 5 and len(wide) == 5
     for name, want in {**team, **wide}.items():
-        r = table[name]
+        r = table[wc.kernel_name(name)]
         assert (r["vgpr_count"], r["agpr_count"], r["group_segment_fixed_size"]) == want, (name, r)
         assert r["vgpr_spill_count"] == 0 and r["private_segment_fixed_size"] == 0, r
 

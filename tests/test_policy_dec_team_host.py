@@ -14,6 +14,7 @@ import pytest
 from tests import policy_cases as pc
 from tests import policy_dec_cases as dc
 from tests import policy_dec_team_cases as tc
+from tests.policy_dec_wide_cases import kernel_name
 
 ROOT = Path(__file__).resolve().parent.parent
 P = 1 << 20      # a fake device pointer: non-null, aligned; never dereferenced by the checks under test
@@ -231,7 +232,7 @@ def table(lib):
 
 @pytest.mark.parametrize("ns,nc", [(3, 2), (4, 2), (5, 2), (6, 3), (12, 4)])
 def test_team_kernels_keep_every_register(table, ns, nc):
-    r = table[f"k_policy_rollout_dec_team<{ns}, {nc}>"]
+    r = table[kernel_name(f"k_policy_rollout_dec_team<{ns}, {nc}>")]
     assert r["vgpr_spill_count"] == 0 and r["private_segment_fixed_size"] == 0, r
     assert r["max_flat_workgroup_size"] == 256, r
     # static LDS: 256 (ns | 1) + 256 * 3 + 256 doubles and 64 ints (and the compiler's padding between them), under 64 KB
@@ -239,8 +240,10 @@ def test_team_kernels_keep_every_register(table, ns, nc):
 
 
 def test_no_further_team_kernel_was_built(table):
-    names = sorted(n for n in table if "k_policy_rollout_dec_team" in n)
-    assert names == sorted(f"k_policy_rollout_dec_team<{ns}, {nc}>" for ns, nc in ((3, 2), (4, 2), (5, 2), (6, 3), (12, 4)))
+    """One kernel text, two word counts: the five one-word instantiations, the five four-word ones, and nothing else."""
+    names = sorted(n for n in table if "k_policy_rollout_dec_team" in n or "k_policy_rollout_dec_wide" in n)
+    assert names == sorted(kernel_name(f"k_policy_rollout_dec_{width}<{ns}, {nc}>") for width in ("team", "wide")
+                           for ns, nc in ((3, 2), (4, 2), (5, 2), (6, 3), (12, 4)))
 
 
 # ---- what stays exactly as it is

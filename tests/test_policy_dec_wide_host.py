@@ -336,7 +336,7 @@ def table(lib):
 
 @pytest.mark.parametrize("ns,nc", FAMILIES)
 def test_wide_kernels_keep_every_register(table, ns, nc):
-    r = table[f"k_policy_rollout_dec_wide<{ns}, {nc}>"]
+    r = table[wc.kernel_name(f"k_policy_rollout_dec_wide<{ns}, {nc}>")]
     assert r["vgpr_spill_count"] == 0 and r["private_segment_fixed_size"] == 0, r
     assert r["max_flat_workgroup_size"] == 256, r
     # static LDS: 256 (ns | 1) + 256 * 3 + 256 doubles and 256 ints (and the compiler's padding between them), under 64 KB
@@ -346,13 +346,15 @@ def test_wide_kernels_keep_every_register(table, ns, nc):
 def test_the_stitch_kernel_and_no_further_wide_kernel(table):
     r = next(v for n, v in table.items() if n.endswith("k_stitch_policy_wide"))
     assert r["vgpr_spill_count"] == 0 and r["private_segment_fixed_size"] == 0, r
-    names = sorted(n for n in table if "k_policy_rollout_dec_wide" in n)
-    assert names == sorted(f"k_policy_rollout_dec_wide<{ns}, {nc}>" for ns, nc in FAMILIES)
+    # one kernel text, two word counts: the five four-word instantiations beside the five one-word ones, and nothing else
+    names = sorted(n for n in table if "k_policy_rollout_dec_team" in n or "k_policy_rollout_dec_wide" in n)
+    assert names == sorted(wc.kernel_name(f"k_policy_rollout_dec_{width}<{ns}, {nc}>") for width in ("team", "wide") for ns, nc in FAMILIES)
 
 
 def test_the_team_kernels_keep_their_figures(table):
-    """The team kernel is restated, not shared: its registers and LDS are what they were (profiles/policy_dec_team_checks.txt)."""
-    r = table["k_policy_rollout_dec_team<12, 4>"]
+    """The one-word instantiations of the shared kernel text: registers and LDS are what the team kernel's were
+    (profiles/policy_dec_team_checks.txt)."""
+    r = table[wc.kernel_name("k_policy_rollout_dec_team<12, 4>")]
     assert (r["vgpr_count"], r["agpr_count"], r["group_segment_fixed_size"]) == (352, 96, 35328), r
-    r = table["k_policy_rollout_dec_team<4, 2>"]
+    r = table[wc.kernel_name("k_policy_rollout_dec_team<4, 2>")]
     assert (r["vgpr_count"], r["agpr_count"], r["group_segment_fixed_size"]) == (179, 0, 18944), r
