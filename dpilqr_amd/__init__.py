@@ -10,8 +10,8 @@ from .bbdynamics import Model, f, integrate, linearize  # noqa: F401
 from .control import ilqrSolver  # noqa: F401
 from .cost import Cost, GameCost, ProximityCost, ReferenceCost, quadraticize_distance  # noqa: F401
 from .dispatch import DistributedPolicy, pairwise_graph, solve_problem_list, solve_scenarios_distributed  # noqa: F401
-from .distributed import (closed_loop_distributed, define_inter_graph_threshold, solve_centralized, solve_distributed, solve_rhc,  # noqa: F401
-                          solve_rhc_closed_loop, solve_rhc_scenarios)
+from .distributed import (closed_loop_distributed, define_inter_graph_threshold, nearest_neighbourhoods, solve_centralized,  # noqa: F401
+                          solve_distributed, solve_rhc, solve_rhc_closed_loop, solve_rhc_scenarios)
 from .dynamics import (BikeDynamics5D, CarDynamics3D, CppModel, DoubleIntDynamics4D, DoubleIntDynamics6D,  # noqa: F401
                        DynamicalModel, HumanDynamics6D, HumanDynamics6DPadded12, HumanDynamicsLin6D, MultiDynamicalModel,
                        QuadcopterDynamics6D, QuadcopterDynamics12D, SymbolicModel, UnicycleDynamics4D)

@@ -134,6 +134,11 @@ ORDER_SIGNATURES = {
 }
 ORDER_SPREAD, ORDER_GROUPED = 1, 2
 
+# ... and of include/dpilqr_nearest.h: the graph with every neighbourhood capped at its m nearest agents -- dispatch_graph_wide's
+# arguments plus max_cluster (behind ignore) and dropped (behind bucket_count)
+_GW = SWARM_SIGNATURES["dpilqr_dispatch_graph_wide"][1]
+NEAREST_SIGNATURES = {"dpilqr_dispatch_graph_nearest": (i32, _GW[:8] + [i32] + _GW[8:15] + [vp] + _GW[15:])}
+
 MAX_AGENTS = 64          # DPILQR_MAX_AGENTS: agents of a sub-problem (cluster), and of a problem on the one-word entries
 MAX_TEAM = 256           # DPILQR_MAX_TEAM: agents of a problem on the wide entries (include/dpilqr_swarm.h)
 
@@ -161,7 +166,7 @@ def load():
                               "(hipcc --offload-arch=gfx950).  dpilqr_amd has no CPU fallback.")
         lib = C.CDLL(str(LIB_PATH))
         for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **SWARM_SIGNATURES, **SWARM_POLICY_SIGNATURES, **SWARM_ADVANCE_SIGNATURES,
-                                   **ORDER_SIGNATURES}.items():
+                                   **ORDER_SIGNATURES, **NEAREST_SIGNATURES}.items():
             fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

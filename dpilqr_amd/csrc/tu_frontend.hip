@@ -5,6 +5,7 @@
 
 #include "dpilqr_hip.h"
 #include "frontend.hpp"
+#include "frontend_nearest.hpp"
 #include "frontend_wide.hpp"
 #include "launch.hpp"
 
@@ -177,6 +178,48 @@ int32_t dpilqr_dispatch_graph_wide(int32_t S, int32_t N, int32_t k, int32_t n_s,
     const unsigned long long* b = reinterpret_cast<const unsigned long long*>(bits);
     hipLaunchKernelGGL(k_graph_bits_wide, dim3((unsigned)S), dim3(kWideThreads), lds_graph, st, S, N, k, n_s, n_words, X, radius,
                        radius_stride, reinterpret_cast<unsigned long long*>(bits));
+    hipLaunchKernelGGL(k_dedup_wide, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, S, k, n_words, b, ignore, rep, size);
+    hipLaunchKernelGGL(k_bucket_sort_wide, dim3(1), dim3(kWideSortThreads), lds_sort, st, S, k, rep, size, order, bucket_start,
+                       bucket_count, slot);
+    HIP_TRY(hipGetLastError());
+    return DPILQR_OK;
+}
+
+// ---- the graph capped at the m nearest agents (frontend_nearest.hpp, include/dpilqr_nearest.h)
+int32_t dpilqr_dispatch_graph_nearest(int32_t S, int32_t N, int32_t k, int32_t n_s, const double* X, const double* radius,
+                                      int64_t radius_stride, const int32_t* ignore, int32_t max_cluster, uint64_t* bits, int32_t* rep,
+                                      int32_t* size, int32_t* order, int32_t* slot, int32_t* bucket_start, int32_t* bucket_count,
+                                      int32_t* dropped, int32_t n_words, void* stream) {
+    const int32_t rc = check_wide("dispatch_graph_nearest", k, n_words);
+    if (rc) return rc;
+    const int m_lim = k < kFrontMaxAgents ? k : kFrontMaxAgents;
+    if (max_cluster < 1 || max_cluster > m_lim)
+        return fail(DPILQR_EINVAL, "dispatch_graph_nearest: max_cluster=%d, a capped neighbourhood has 1 .. min(k, %d) = %d members",
+                    max_cluster, kFrontMaxAgents, m_lim);
+    if (S < 0 || N < 1 || n_s < 2 || !X || !radius || !bits || !rep || !size || !order || !slot || !bucket_start || !bucket_count)
+        return fail(DPILQR_EINVAL, "dispatch_graph_nearest: bad argument");
+    hipStream_t st = as_stream(stream);
+    if (S == 0) {
+        HIP_TRY(hipMemsetAsync(bucket_start, 0, sizeof(int32_t) * (k + 1), st));
+        HIP_TRY(hipMemsetAsync(bucket_count, 0, sizeof(int32_t) * (k + 1), st));
+        return DPILQR_OK;
+    }
+    const size_t lds_graph = graph_nearest_lds_bytes(N, k), lds_sort = sizeof(int32_t) * (k + 1) * kWideSortThreads;
+    unsigned long long* b = reinterpret_cast<unsigned long long*>(bits);
+#define NEAREST_WORDS(NW)                                                                                                          \
+    case NW: {      /* both above 64 KiB for the largest teams: ask before anything of this call is queued */                      \
+        int32_t rc_lds = allow_lds(k_graph_bits_nearest<NW>, lds_graph);                                                            \
+        if (!rc_lds) rc_lds = allow_lds(k_bucket_sort_wide, lds_sort);                                                             \
+        if (rc_lds) return rc_lds;                                                                                                 \
+        hipLaunchKernelGGL(k_graph_bits_nearest<NW>, dim3((unsigned)S), dim3(kWideThreads), lds_graph, st, S, N, k, n_s, max_cluster, \
+                           X, radius, radius_stride, b, dropped);                                                                  \
+    } break;
+    switch (n_words) {
+        NEAREST_WORDS(1) NEAREST_WORDS(2) NEAREST_WORDS(3) NEAREST_WORDS(4)
+        default: return fail(DPILQR_EINVAL, "dispatch_graph_nearest: n_words=%d", n_words);      // (check_wide holds 1 .. 4)
+    }
+#undef NEAREST_WORDS
+    const int64_t n = (int64_t)S * k;
     hipLaunchKernelGGL(k_dedup_wide, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, S, k, n_words, b, ignore, rep, size);
     hipLaunchKernelGGL(k_bucket_sort_wide, dim3(1), dim3(kWideSortThreads), lds_sort, st, S, k, rep, size, order, bucket_start,
                        bucket_count, slot);

@@ -107,6 +107,15 @@ def pairwise_graph(X, radius, k, n_s):
     return adj
 
 
+def checked_max_cluster(max_cluster, k):
+    """The cap of a neighbourhood as the device entry takes it: an integer 1 .. 64 (bool is not one), clamped to min(m, k)."""
+    import numbers
+    if isinstance(max_cluster, bool) or not isinstance(max_cluster, numbers.Integral) or not 1 <= int(max_cluster) <= _lib.MAX_AGENTS:
+        raise ValueError(f"max_cluster={max_cluster!r}: a neighbourhood is capped at an integer number of agents, 1 .. {_lib.MAX_AGENTS} "
+                         "(None: no cap)")
+    return min(int(max_cluster), int(k))
+
+
 class ScenarioFrontEnd:
     """Device-side front and back end of solve_distributed for S scenarios of one k-agent problem (include/dpilqr_hip.h
     section 7, csrc/frontend.hpp): interaction graphs as bit masks, one representative per distinct neighbourhood (the
@@ -119,9 +128,17 @@ class ScenarioFrontEnd:
     (wide=True puts such a team on the wide entries with n_words = 1: the same arrays, bit for bit).
     A cluster (sub-problem) has at most 64 agents in either form: a populated cluster size beyond that is a ValueError before any
     solve.  The policy of a wide team is stitched by stitch_policy_wide (policy="wide").  Not built for wide teams: stitch_policy,
-    pack_rows / scatter_rows (policy=True, shard=)."""
+    pack_rows / scatter_rows (policy=True, shard=).
 
-    def __init__(self, d, X, U, radius, xf, ignore=None, wide=None):
+    max_cluster=m (an integer 1 .. 64, clamped to min(m, k); anything else is a ValueError before any device work) caps every
+    neighbourhood at its m nearest agents (dpilqr_dispatch_graph_nearest, include/dpilqr_nearest.h): agent i keeps itself and the
+    m - 1 members of its neighbourhood that are smallest under (key(i, j), j), key = the smallest sampled planar distance, ties
+    to the lower index; a neighbourhood of at most m members is kept as it is.  self.dropped (S*k,) int32 holds how many members
+    each agent lost and self.max_cluster the clamped cap.  With wide=False (k <= 64) the entry is called with n_words = 1 and
+    `bits` stays (S*k,).  No cluster exceeds 64 agents then, so the refusal above cannot fire.  The default None is the graph without a cap,
+    through the entries it always took."""
+
+    def __init__(self, d, X, U, radius, xf, ignore=None, wide=None, max_cluster=None):
         self.lib = _lib.load()
         self.d = d
         k = self.k = d["k"]
@@ -131,6 +148,8 @@ class ScenarioFrontEnd:
         if k > _lib.MAX_AGENTS and not self.wide:
             raise ValueError(f"{k} agents need the wide entries (wide=False serves at most {_lib.MAX_AGENTS})")
         self.n_words = nw = (k + 63) // 64
+        self.max_cluster = None if max_cluster is None else checked_max_cluster(max_cluster, k)
+        self.dropped = None
         self.X = to_dev(X).contiguous(); self.U = to_dev(U).contiguous()
         self.S, self.N = int(self.X.shape[0]), int(self.X.shape[1])
         self.T = int(self.U.shape[1])
@@ -147,7 +166,11 @@ class ScenarioFrontEnd:
         self.bstart, self.bcount = empty((k + 1,), torch.int32), empty((k + 1,), torch.int32)
         graph_args = (S, self.N, k, self.n_s, ptr(self.X), ptr(rad), 1, ptr(ign), ptr(self.bits), ptr(self.rep), ptr(self.size),
                       ptr(self.order), ptr(self.slot), ptr(self.bstart), ptr(self.bcount))
-        if self.wide:
+        if self.max_cluster is not None:
+            self.dropped = empty((n,), torch.int32)
+            _lib.check(self.lib.dpilqr_dispatch_graph_nearest(*graph_args[:8], self.max_cluster, *graph_args[8:], ptr(self.dropped), nw,
+                                                              stream_handle()))
+        elif self.wide:
             _lib.check(self.lib.dpilqr_dispatch_graph_wide(*graph_args, nw, stream_handle()))
         else:
             _lib.check(self.lib.dpilqr_dispatch_graph(*graph_args, stream_handle()))
@@ -387,8 +410,18 @@ def solve_scenarios_distributed(problem, X, U, radius, xf=None, window=None, con
     info["cluster_bits"] is then (S, k, ceil(k / 64)) -- word w, bit b = agent 64 w + b -- instead of (S, k).  Every cluster still
     has at most 64 agents and lies within the solver's own limits.  The closed-loop rollout of such a team: policy="wide".  Not
     built for such teams: policy=True and shard= (each a ValueError before any device work), fp32.
+
+    max_cluster=m (a keyword of its own, taken out of **kwargs before the solver's are -- the named parameters stay as they were; an
+    integer 1 .. 64, clamped to min(m, k); opt-in, absent or None = today's graph through today's entries): every agent
+    plans with at most m agents -- itself and the m - 1 nearest of its neighbours (ScenarioFrontEnd, include/dpilqr_nearest.h:
+    smallest sampled planar distance, ties to the lower index) --, so a team whose neighbourhoods exceed 64 agents, or the solver's
+    own n_x <= 240, is planned instead of refused.  info["max_cluster"] is the clamped cap and info["n_dropped"] (S, k) int32 the
+    members every agent's neighbourhood lost (a host array).  The masks need not be symmetric then.  It combines with policy=True,
+    policy="wide", ignore_ids, audit, device_out and with shard= (k <= 64): pack_rows / scatter_rows read the capped masks as
+    they read any others.
     """
     from .sharding import shard_bounds
+    max_cluster = kwargs.pop("max_cluster", None)
     if policy and (shard is not None or ignore_ids):
         raise ValueError("solve_scenarios_distributed: policy=True serves neither shard= nor ignore_ids (every agent of every "
                          "scenario needs its sub-problem's gains on this device)")
@@ -407,7 +440,7 @@ def solve_scenarios_distributed(problem, X, U, radius, xf=None, window=None, con
     solve_kw = solve_kwargs(kwargs, "solve_scenarios_distributed")
     from time import perf_counter as pc
     t0 = pc()
-    fe = ScenarioFrontEnd(d, X, U, radius, xf, ignore, wide=True if wide_policy else None)
+    fe = ScenarioFrontEnd(d, X, U, radius, xf, ignore, wide=True if wide_policy else None, max_cluster=max_cluster)
     t_front = pc() - t0                      # uploads, graph, de-duplication, bucket sort, the one host read
     S, T = fe.S, fe.T
     sizes = fe.sizes()
@@ -448,6 +481,9 @@ def solve_scenarios_distributed(problem, X, U, radius, xf=None, window=None, con
     info = dict(n_subproblems=int(S * k), n_unique=int(fe.counts.sum()),
                 sizes={int(kc): int(fe.counts[kc]) for kc in sizes}, n_bwd=n_bwd_total,
                 seconds=dict(front_end=t_front, solves=t_solve))
+    if fe.max_cluster is not None:
+        info["max_cluster"] = fe.max_cluster
+        info["n_dropped"] = fe.dropped.cpu().numpy().reshape(-1)[:S * k].reshape(S, k)
     if audit:
         info["audit"] = {int(kc): r[5] for kc, r in results if r is not None}
     if shard is not None:

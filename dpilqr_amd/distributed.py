@@ -32,20 +32,56 @@ def define_inter_graph_threshold(X, radius, x_dims, ids):
     return {id_: sorted(members) for id_, members in graph.items()}
 
 
-def solve_distributed(problem, X, U, radius, ignore_ids=None, pool=None, verbose=True, **kwargs):
+def nearest_neighbourhoods(X, radius, x_dims, ids, max_cluster):
+    """define_inter_graph_threshold with every neighbourhood capped at its max_cluster nearest agents -- the definition of
+    include/dpilqr_nearest.h in NumPy.  Over the sampled rows r (the same rows), d_r(i, j) = sqrt(dx*dx + dy*dy) over the planar
+    positions, key(i, j) = min_r d_r(i, j) (a comparison with a NaN is false: a NaN distance is never the minimum, a NaN key
+    never a neighbour), nbr(i) = {i} + {j : key(i, j) < 2 radius}.  A neighbourhood of at most m = min(max_cluster, k) members is
+    kept; a larger one becomes i and the m - 1 members j != i smallest under the lexicographic order on (key(i, j), j): ties go
+    to the lower agent index.  The result need not be symmetric.  Returns what define_inter_graph_threshold returns:
+    {id: sorted ids, the agent's own included}.  max_cluster: an integer 1 .. 64."""
+    from .dispatch import checked_max_cluster
+    X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+    k = len(ids)
+    m = checked_max_cluster(max_cluster, k)
+    n_rows = X.shape[0]
+    rows = X[0:n_rows + 1:max(n_rows // 10, 1)]
+    start = np.concatenate([[0], np.cumsum(x_dims)[:-1]]).astype(int)
+    px, py = rows[:, start], rows[:, start + 1]                       # (rows, k)
+    dx, dy = px[:, :, None] - px[:, None, :], py[:, :, None] - py[:, None, :]
+    with np.errstate(invalid="ignore"):
+        key = np.fmin.reduce(np.sqrt(dx * dx + dy * dy), axis=0)      # fmin skips a NaN; all NaN stays NaN and compares false
+        near = key < 2 * radius
+    np.fill_diagonal(near, False)
+    ids_np = np.array(ids)                                            # neighbours as NumPy integers, as define_inter_graph_threshold's (Q10)
+    graph = {}
+    for i, id_ in enumerate(ids):
+        cand = np.nonzero(near[i])[0]
+        if cand.size + 1 > m:
+            cand = cand[np.lexsort((cand, key[i, cand]))][:m - 1]
+        graph[id_] = sorted([id_] + [ids_np[j] for j in cand])
+    return graph
+
+
+def solve_distributed(problem, X, U, radius, ignore_ids=None, pool=None, verbose=True, max_cluster=None, **kwargs):
     """One sub-problem per agent (its closed neighbourhood), all solved in one batched dispatch.
 
     Returns X_dec (N+1, n_x), U_dec (N, n_u), J_full, solve_info {id: (seconds, neighbourhood)}.
     `pool` is accepted for signature compatibility; the device batch takes its place.  `ignore_ids=None`
     means "ignore nobody" (the reference raises TypeError there, quirk Q9).  Teams of up to 256 agents are served (J_full of
-    more than 64 agents through ProblemBatch.rollout_wide); every neighbourhood must lie within the solver's own limits."""
+    more than 64 agents through ProblemBatch.rollout_wide); every neighbourhood must lie within the solver's own limits.
+    max_cluster=m (an integer 1 .. 64; None: no cap): every agent plans with itself and at most the m - 1 nearest of its
+    neighbours -- the graph is nearest_neighbourhoods(X, radius, x_dims, ids, m); solve_rhc passes it on as it passes radius."""
     X = np.atleast_2d(np.asarray(X, dtype=np.float64)); U = np.asarray(U, dtype=np.float64)
     x_dims, u_dims = problem.game_cost.x_dims, problem.game_cost.u_dims
     N, n_s, n_c, ids = U.shape[0], x_dims[0], u_dims[0], problem.ids
     ignore_ids = list(ignore_ids) if ignore_ids else []
     if any(id_ not in ids for id_ in ignore_ids):
         raise ValueError(f"Some of {ignore_ids} not in {ids}.")
-    graph = define_inter_graph_threshold(X, radius, x_dims, ids)
+    if max_cluster is None:
+        graph = define_inter_graph_threshold(X, radius, x_dims, ids)
+    else:
+        graph = nearest_neighbourhoods(X, radius, x_dims, ids, max_cluster)
     if verbose:
         print("=" * 80 + f"\nInteraction Graph: {graph}")
     x0_split = split_graph(X[np.newaxis, 0], x_dims, graph)
@@ -69,7 +105,8 @@ def solve_distributed(problem, X, U, radius, ignore_ids=None, pool=None, verbose
     return X_dec, U_dec, J_full, solve_info
 
 
-def closed_loop_distributed(problem, X, U, radius, x0s, W=None, u_lim=None, mu=0.0, trajectories=False, wide=False, **solve_kwargs):
+def closed_loop_distributed(problem, X, U, radius, x0s, W=None, u_lim=None, mu=0.0, trajectories=False, wide=False, max_cluster=None,
+                            **solve_kwargs):
     """The closed loop of solve_distributed's solution for one scenario: solve the sub-problems from (X, U) as
     solve_scenarios_distributed does, take every sub-problem's gains from one backward pass at its solution (regularisation
     mu, as ilqrSolver.closed_loop), and run the agents' own feedback laws -- each over its neighbourhood only -- on the full
@@ -77,7 +114,9 @@ def closed_loop_distributed(problem, X, U, radius, x0s, W=None, u_lim=None, mu=0
     Returns host arrays: J, min_sep (n_samples,), goal_dist (n_samples, k), X_dec, U_dec of the solve and, with
     trajectories=True, X (n_samples, N+1, n_x), U (n_samples, N, n_u).  Device problems only.
     wide=True: solve_scenarios_distributed(policy="wide") -- any team of up to 256 agents, multi-word neighbourhood masks,
-    ProblemBatch.policy_rollout_dec_wide; the default serves teams of up to 64 agents as ever."""
+    ProblemBatch.policy_rollout_dec_wide; the default serves teams of up to 64 agents as ever.
+    max_cluster=m (an integer 1 .. 64; None: no cap): solve_scenarios_distributed(max_cluster=m) -- every agent plans, and feeds
+    back, over itself and at most the m - 1 nearest of its neighbours."""
     from .lowering import is_lowerable
     if not is_lowerable(problem):
         raise NotImplementedError("closed_loop_distributed runs the policy on the device and needs a problem built from the "
@@ -85,13 +124,16 @@ def closed_loop_distributed(problem, X, U, radius, x0s, W=None, u_lim=None, mu=0
                                   "Python callables")
     X = np.atleast_2d(np.asarray(X, dtype=np.float64)); U = np.asarray(U, dtype=np.float64)
     n_x = problem.dynamics.n_x
+    if max_cluster is not None:
+        from .dispatch import checked_max_cluster
+        checked_max_cluster(max_cluster, problem.n_agents)
     x0s = np.asarray(x0s, dtype=np.float64)
     if x0s.ndim != 2 or x0s.shape[1] != n_x:
         raise ValueError(f"closed_loop_distributed: x0s has shape {x0s.shape}, expected (n_samples, {n_x})")
     if U.ndim != 2 or X.shape[1] != n_x or X.shape[0] not in (1, U.shape[0] + 1):
         raise ValueError(f"closed_loop_distributed: X {X.shape}, U {U.shape}: expected (N+1 or 1, {n_x}) and (N, n_u)")
     X_dec, U_dec, _, info = solve_scenarios_distributed(problem, X[None], U[None], radius, device_out=True, policy="wide" if wide else True,
-                                                        policy_mu=float(mu), **solve_kwargs)
+                                                        policy_mu=float(mu), max_cluster=max_cluster, **solve_kwargs)
     r = info["policy"].rollout(x0s[None], W=None if W is None else np.asarray(W, dtype=np.float64)[None], u_lim=u_lim,
                                trajectories=trajectories)
     out = {key: v[0].cpu().numpy() for key, v in r.items()}
@@ -164,7 +206,8 @@ def solve_rhc(problem, x0, N, *args, centralized=True, n_d=2, step_size=1, J_con
 
 
 def solve_rhc_scenarios(problem, x0, N, radius, xf=None, U0=None, centralized=False, n_d=2, step_size=1,
-                        J_converge=None, dist_converge=None, t_diverge=None, window=None, i_trial=None, rows=None, **kwargs):
+                        J_converge=None, dist_converge=None, t_diverge=None, window=None, i_trial=None, rows=None, max_cluster=None,
+                        **kwargs):
     """solve_rhc (distributed.py:106-221) for S Monte-Carlo scenarios of one k-agent problem in lock step: every
     receding-horizon round is ONE batched solve over the scenarios still running (solve_scenarios_distributed, or one
     ProblemBatch when centralized), with the reference's warm-start shift and stopping rules applied per scenario.
@@ -178,6 +221,8 @@ def solve_rhc_scenarios(problem, x0, N, radius, xf=None, U0=None, centralized=Fa
     i_trial: their trial numbers (a sequence of S, or one value).  The `times` field is wall-clock there and here: each
     agent is given its share of the round's batched solve.  kwargs: n_lqr_iter, tol, t_kill reach every solve.
     Not built for teams of more than 64 agents (centralized or not): ValueError before any device work.
+    max_cluster=m (an integer 1 .. 64; None: no cap; the distributed branch): every round's solve_scenarios_distributed caps the
+    neighbourhoods at their m nearest agents, and the rows' `subgraphs` field shows the capped neighbourhoods.
     Returns a list of S tuples (X_full, U_full, J_full, converged), what solve_rhc returns plus its `converged` flag."""
     import torch
     from .batch import ProblemBatch
@@ -192,6 +237,11 @@ def solve_rhc_scenarios(problem, x0, N, radius, xf=None, U0=None, centralized=Fa
     if k > _lib.MAX_AGENTS:
         raise ValueError(f"solve_rhc_scenarios is not built for teams of more than {_lib.MAX_AGENTS} agents (this one has {k}): "
                          "solve_scenarios_distributed and solve_distributed serve them, round by round")
+    if max_cluster is not None:
+        from .dispatch import checked_max_cluster
+        checked_max_cluster(max_cluster, k)
+        if centralized:
+            raise ValueError("solve_rhc_scenarios: max_cluster caps the neighbourhoods of the distributed solve (centralized=False)")
     n_x, n_u = problem.dynamics.n_x, problem.dynamics.n_u
     n_s = n_x // k
     x0 = np.asarray(x0, dtype=np.float64).reshape(-1, n_x)
@@ -238,7 +288,7 @@ def solve_rhc_scenarios(problem, x0, N, radius, xf=None, U0=None, centralized=Fa
         else:
             Xin = xi[ia][:, None, :] if X is None else X[ia]
             Xa, Ua, Ja, info = solve_scenarios_distributed(problem, Xin, U[ia], radius, xf=xf_d[ia], window=window, device_out=True,
-                                                           desc=d, **solve_kw)
+                                                           desc=d, max_cluster=max_cluster, **solve_kw)
             bits = info["cluster_bits"]
         if X is None:
             X = torch.zeros((S, N + 1, n_x), dtype=torch.float64, device=xi.device)
@@ -303,7 +353,7 @@ def solve_rhc_scenarios(problem, x0, N, radius, xf=None, U0=None, centralized=Fa
 
 def solve_rhc_closed_loop(problem, x0, N, radius=None, xf=None, U0=None, centralized=True, feedback=True, W=None, u_lim=None,
                           policy_mu=0.0, n_d=2, step_size=1, dist_converge=None, J_converge=None, max_steps=None, window=None,
-                          large=False, team=False, wide=False, **kwargs):
+                          large=False, team=False, wide=False, max_cluster=None, **kwargs):
     """The receding-horizon loop on a REAL plant, for S scenarios in lock step: plan, execute step_size steps of the plan's
     feedback policy under a disturbance and actuator limits, re-plan from where the plant ended up.  solve_rhc and
     solve_rhc_scenarios keep the reference's ideal plant (xi = X[step_size]); here every round is one batched solve over the
@@ -336,6 +386,10 @@ def solve_rhc_closed_loop(problem, x0, N, radius=None, xf=None, U0=None, central
     ProblemBatch.policy_advance_dec_wide -- DistributedPolicy.advance(..., wide=True) with feedback, the stitched plan open loop
     without --, and the final state's terminal cost is ProblemBatch.cost_wide.  It is opt-in too: without it every refusal is
     as before, a team of more than 64 agents included.
+    max_cluster=m (an integer 1 .. 64; None: no cap) serves every distributed route -- the small one, team=True, wide=True --:
+    each round's solve_scenarios_distributed caps the neighbourhoods at their m nearest agents (include/dpilqr_nearest.h), the
+    policy's masks are the capped ones and the advance reads them as any others; a dense team (a clique of 64, a swarm whose
+    neighbourhoods exceed 64 agents) is planned round by round instead of refused.  With centralized=True it is a ValueError.
     Not built: fp32, shard=, ignore_ids; the wide route as a default.  Device problems only."""
     import torch
     from . import _lib
@@ -352,6 +406,11 @@ def solve_rhc_closed_loop(problem, x0, N, radius=None, xf=None, U0=None, central
     n_x, n_u = problem.dynamics.n_x, problem.dynamics.n_u
     k = problem.n_agents      # (lowerable: one cost and one (n_s, n_c) per agent)
     n_s, n_c = n_x // k, n_u // k
+    if max_cluster is not None:
+        from .dispatch import checked_max_cluster
+        checked_max_cluster(max_cluster, k)
+        if centralized:
+            raise ValueError("solve_rhc_closed_loop: max_cluster caps the neighbourhoods of the distributed loop (centralized=False)")
     if wide:      # the wide entries, whatever the size: none of the routes below
         if centralized:
             raise ValueError("solve_rhc_closed_loop: wide=True is the distributed loop (centralized=False) of a team of up to "
@@ -447,7 +506,8 @@ def solve_rhc_closed_loop(problem, x0, N, radius=None, xf=None, U0=None, central
             Xin = state["x_cur"][ia][:, None, :] if first else state["X_next"][ia]
             Xa, Ua, Ja, info = solve_scenarios_distributed(problem, Xin, state["U_next"][ia], radius, xf=xf_d[ia], window=window,
                                                            device_out=True, desc=d, policy_mu=float(policy_mu),
-                                                           policy="wide" if wide and feedback else bool(feedback), **solve_kw)
+                                                           policy="wide" if wide and feedback else bool(feedback),
+                                                           max_cluster=max_cluster, **solve_kw)
             if feedback:
                 info["policy"].advance(h, state, scen=scen, W=W_d, u_lim=lim_d, n_d=n_d, team=team, wide=wide)
             else:
