@@ -139,6 +139,13 @@ ORDER_SPREAD, ORDER_GROUPED = 1, 2
 _GW = SWARM_SIGNATURES["dpilqr_dispatch_graph_wide"][1]
 NEAREST_SIGNATURES = {"dpilqr_dispatch_graph_nearest": (i32, _GW[:8] + [i32] + _GW[8:15] + [vp] + _GW[15:])}
 
+# ... and of include/dpilqr_swarm_study.h: a trial's inputs drawn on the device -- S, seed0, seeds, k, n_s, n_d, var, energy,
+# n_warm, N, n_u, warm_scale, x0, xf, U_a, U_b, stream
+SWARM_STUDY_SIGNATURES = {
+    "dpilqr_trial_inputs": (i32, [i32, C.c_int64, vp, i32, i32, i32, C.c_double, C.c_double, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp]),
+}
+TRIAL_INPUTS_LDS = 37888     # DPILQR_TRIAL_INPUTS_LDS
+
 MAX_AGENTS = 64          # DPILQR_MAX_AGENTS: agents of a sub-problem (cluster), and of a problem on the one-word entries
 MAX_TEAM = 256           # DPILQR_MAX_TEAM: agents of a problem on the wide entries (include/dpilqr_swarm.h)
 
@@ -166,7 +173,7 @@ def load():
                               "(hipcc --offload-arch=gfx950).  dpilqr_amd has no CPU fallback.")
         lib = C.CDLL(str(LIB_PATH))
         for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **SWARM_SIGNATURES, **SWARM_POLICY_SIGNATURES, **SWARM_ADVANCE_SIGNATURES,
-                                   **ORDER_SIGNATURES, **NEAREST_SIGNATURES}.items():
+                                   **ORDER_SIGNATURES, **NEAREST_SIGNATURES, **SWARM_STUDY_SIGNATURES}.items():
             fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -55,6 +55,30 @@ def trial_inputs(n_agents, n_states, n_u, N, energy, n_d, seed):
     return x0, xf, U_c, U_d
 
 
+def trial_inputs_batch(n_agents, n_states, n_u, N, energy, n_d, seeds):
+    """trial_inputs for the S trials seeded `seeds`, drawn on the device (dpilqr_trial_inputs, include/dpilqr_swarm_study.h): device
+    tensors x0, xf (S, n_agents * n_states) and U_c, U_d (S, N, n_u), bit for bit trial_inputs' four arrays of every seed, for
+    teams of 1 .. 256 agents -- var = n_agents / 2 and the warm starts scaled by 0.01 as there.  seeds: any sequence of integers
+    of [0, 2^32); a consecutive run is passed as its first seed, anything else as a device array."""
+    import torch
+    from . import _lib
+    from .device import empty, ptr, stream_handle, to_dev
+    seeds = [int(s) for s in seeds]
+    S = len(seeds)
+    if not 1 <= n_agents <= _lib.MAX_TEAM:
+        raise ValueError(f"trial_inputs_batch: {n_agents} agents -- the device generator serves teams of 1 .. {_lib.MAX_TEAM}")
+    if any(not 0 <= s < 2 ** 32 for s in seeds):
+        raise ValueError("trial_inputs_batch: np.random.seed takes seeds of [0, 2^32)")
+    x0 = empty((S, n_agents * n_states)); xf = empty((S, n_agents * n_states))
+    U_c = empty((S, N, n_u)); U_d = empty((S, N, n_u))
+    consecutive = all(b == a + 1 for a, b in zip(seeds, seeds[1:]))
+    seeds_d = None if consecutive else to_dev(torch.tensor(seeds, dtype=torch.int64), torch.int64)
+    _lib.check(_lib.load().dpilqr_trial_inputs(S, seeds[0] if S and consecutive else 0, ptr(seeds_d), n_agents, n_states, n_d,
+                                               float(n_agents / 2), float(energy or 0.0), 2, N, n_u, 0.01, ptr(x0), ptr(xf), ptr(U_c),
+                                               ptr(U_d), stream_handle()))
+    return x0, xf, U_c, U_d
+
+
 def weights_of(model, n_states):
     """analysis.py:62-69"""
     if model in (DoubleIntDynamics4D, UnicycleDynamics4D):
@@ -79,31 +103,56 @@ def build_problem(model, n_agents, dt, radius, xf, n_d):
 
 
 def multi_agent_run(model, x_dims, dt, N, radius, energy=10.0, n_d=2, trials=(0,), seed0=0, emit=logging.info, window=None,
-                    **kwargs):
+                    branches=(True, False), wide=False, max_cluster=None, device_inputs=False, **kwargs):
     """multi_agent_run (analysis.py:35-107) for all `trials` of one (model, team size) at once: both branches, every
     receding-horizon round of every trial one batched solve.  kwargs as the reference passes them: t_kill, dist_converge,
     t_diverge (i_trial is replaced by `trials`; energy is consumed here).  Emits the rows in the reference's order and
-    returns {trial: ((Xc, Uc, Jc, converged), (Xd, Ud, Jd, converged))}."""
+    returns {trial: ((Xc, Uc, Jc, converged), (Xd, Ud, Jd, converged))}.
+    branches: which of the two loops run, as values of `centralized` -- (True, False) both, (False,) the distributed loop alone,
+    whose rows are then the only ones emitted (in the order they have in the two-branch run) and whose tuple is the only one
+    returned per trial.  A trial draws what it always draws -- both warm starts, the distributed loop takes the second -- so the
+    rows of a branch do not depend on which other branch ran.
+    wide, max_cluster reach the distributed branch's solve_rhc_scenarios: with wide=True a swarm of up to 256 agents is studied,
+    distributed only (no centralized solve is built above n_x = 240: wide=True with True in branches is a ValueError).
+    device_inputs=True draws the trials' inputs on the device (trial_inputs_batch: the same bits) and hands the device tensors
+    to the loops; they never come to the host."""
     if not len(set(x_dims)) == 1:
         raise ValueError("Dynamics dimensions must be consistent")
+    branches = tuple(bool(b) for b in branches)
+    if not branches or len(set(branches)) != len(branches):
+        raise ValueError(f"multi_agent_run: branches={branches}, expected a non-empty selection of (True, False) without repeats")
+    if wide and True in branches:
+        raise ValueError("multi_agent_run: wide=True studies the distributed loop alone (branches=(False,)); no centralized solve "
+                         "is built for the teams it serves")
     kwargs.pop("i_trial", None); kwargs.pop("verbose", None)
     n_agents, n_states = len(x_dims), x_dims[0]
     trials = list(trials)
     n_u = n_agents * model(-1).n_u
-    drawn = [trial_inputs(n_agents, n_states, n_u, N, energy, n_d, seed_of(model, n_agents, i, seed0)) for i in trials]
-    x0 = np.stack([d[0].ravel() for d in drawn]); xf = np.stack([d[1].ravel() for d in drawn])
-    problem = build_problem(model, n_agents, dt, radius, xf[0], n_d)     # per-trial goals go in as `xf` below
+    seeds = [seed_of(model, n_agents, i, seed0) for i in trials]
+    if device_inputs:
+        x0, xf, U_c, U_d = trial_inputs_batch(n_agents, n_states, n_u, N, energy, n_d, seeds)
+        warm = {True: U_c, False: U_d}
+        xf_first = xf[0].cpu().numpy()
+    else:
+        drawn = [trial_inputs(n_agents, n_states, n_u, N, energy, n_d, seed) for seed in seeds]
+        x0 = np.stack([d[0].ravel() for d in drawn]); xf = np.stack([d[1].ravel() for d in drawn])
+        warm = {centralized: np.stack([d[col] for d in drawn]) for centralized, col in ((True, 2), (False, 3)) if centralized in branches}
+        xf_first = xf[0]
+    problem = build_problem(model, n_agents, dt, radius, xf_first, n_d)     # per-trial goals go in as `xf` below
     out, rows = {}, {}
-    for centralized, col in ((True, 2), (False, 3)):
+    for centralized in (True, False):
+        if centralized not in branches:
+            continue
         r = []
-        res = solve_rhc_scenarios(problem, x0, N, radius, xf=xf, U0=np.stack([d[col] for d in drawn]), centralized=centralized,
-                                  n_d=n_d, step_size=STEP_SIZE, i_trial=trials, rows=r, window=window, **kwargs)
+        own = {} if centralized else {key: v for key, v in (("wide", wide), ("max_cluster", max_cluster)) if v}
+        res = solve_rhc_scenarios(problem, x0, N, radius, xf=xf, U0=warm[centralized], centralized=centralized,
+                                  n_d=n_d, step_size=STEP_SIZE, i_trial=trials, rows=r, window=window, **own, **kwargs)
         rows[centralized] = r
         for j, i in enumerate(trials):
             out.setdefault(i, []).append(res[j])
     for j, i in enumerate(trials):
         for centralized in (True, False):
-            for row in rows[centralized][j]:
+            for row in rows.get(centralized, [[]] * len(trials))[j]:
                 emit(row)
     return {i: tuple(v) for i, v in out.items()}
 
@@ -135,9 +184,13 @@ def setup_logger(limit_solve_time, log_file=None):
 
 
 def monte_carlo_analysis(limit_solve_time=False, n_trials=2, n_agents_iter=(3, 4, 5, 6, 7), models=MODELS, dt=0.1, N=50,
-                         energy=10.0, radius=0.50, seed0=0, log_file=None, emit=None, window=None):
+                         energy=10.0, radius=0.50, seed0=0, log_file=None, emit=None, window=None, branches=(True, False), wide=False,
+                         max_cluster=None, device_inputs=False):
     """monte_carlo_analysis (analysis.py:126-174): the same loops, constants and stopping rules; the innermost loop (the
-    trials) is the batch.  n_trials may be thousands -- that is what the batched path is for."""
+    trials) is the batch.  n_trials may be thousands -- that is what the batched path is for.
+    branches, wide, max_cluster, device_inputs: multi_agent_run's, passed through -- branches=(False,), wide=True studies
+    swarms of up to 256 agents, distributed only.  energy may be a callable of n_agents: the reference's fixed 10.0 puts 256
+    agents within one radius of each other, a swarm needs an energy that grows with the team."""
     if emit is None:
         setup_logger(limit_solve_time, log_file)
         emit = logging.getLogger(LOGGER_NAME).info
@@ -153,6 +206,7 @@ def monte_carlo_analysis(limit_solve_time=False, n_trials=2, n_agents_iter=(3, 4
             n_d = 3 if model is QuadcopterDynamics6D else 2
             x_dims = [model(-1).n_x] * n_agents
             results[(model.__name__, n_agents)] = multi_agent_run(
-                model, x_dims, dt, N, radius, n_d=n_d, t_kill=t_kill, dist_converge=0.1, t_diverge=t_diverge, energy=energy,
-                trials=range(n_trials), seed0=seed0, emit=emit, window=window, verbose=False)
+                model, x_dims, dt, N, radius, n_d=n_d, t_kill=t_kill, dist_converge=0.1, t_diverge=t_diverge,
+                energy=energy(n_agents) if callable(energy) else energy, trials=range(n_trials), seed0=seed0, emit=emit, window=window,
+                branches=branches, wide=wide, max_cluster=max_cluster, device_inputs=device_inputs, verbose=False)
     return results

@@ -419,9 +419,14 @@ def solve_scenarios_distributed(problem, X, U, radius, xf=None, window=None, con
     members every agent's neighbourhood lost (a host array).  The masks need not be symmetric then.  It combines with policy=True,
     policy="wide", ignore_ids, audit, device_out and with shard= (k <= 64): pack_rows / scatter_rows read the capped masks as
     they read any others.
+
+    wide=True (a keyword of its own like max_cluster; opt-in) puts a team of up to 64 agents on the wide front end as policy="wide"
+    does, without taking a policy: the same X_dec, U_dec and J_full bit for bit, info["cluster_bits"] of shape (S, k, 1).  A larger
+    team is on the wide front end anyway.  Not with shard=.
     """
     from .sharding import shard_bounds
     max_cluster = kwargs.pop("max_cluster", None)
+    wide_front = bool(kwargs.pop("wide", False))
     if policy and (shard is not None or ignore_ids):
         raise ValueError("solve_scenarios_distributed: policy=True serves neither shard= nor ignore_ids (every agent of every "
                          "scenario needs its sub-problem's gains on this device)")
@@ -430,6 +435,8 @@ def solve_scenarios_distributed(problem, X, U, radius, xf=None, window=None, con
     if isinstance(policy, str) and policy != "wide":
         raise ValueError(f"solve_scenarios_distributed: policy={policy!r}, expected False, True or 'wide'")
     wide_policy = isinstance(policy, str)
+    if wide_front and shard is not None:
+        raise ValueError("solve_scenarios_distributed: wide=True does not serve shard= (pack_rows / scatter_rows read one-word masks)")
     if k > _lib.MAX_AGENTS and ((policy and not wide_policy) or shard is not None):
         raise ValueError(f"solve_scenarios_distributed: {'policy=True' if policy and not wide_policy else 'shard='} is not built for teams of more than "
                          f"{_lib.MAX_AGENTS} agents (this one has {k})")
@@ -440,7 +447,7 @@ def solve_scenarios_distributed(problem, X, U, radius, xf=None, window=None, con
     solve_kw = solve_kwargs(kwargs, "solve_scenarios_distributed")
     from time import perf_counter as pc
     t0 = pc()
-    fe = ScenarioFrontEnd(d, X, U, radius, xf, ignore, wide=True if wide_policy else None, max_cluster=max_cluster)
+    fe = ScenarioFrontEnd(d, X, U, radius, xf, ignore, wide=True if wide_policy or wide_front else None, max_cluster=max_cluster)
     t_front = pc() - t0                      # uploads, graph, de-duplication, bucket sort, the one host read
     S, T = fe.S, fe.T
     sizes = fe.sizes()

@@ -155,6 +155,21 @@ def rhc_log_row(model_name, n_agents, i_trial, centralized, last, t, J, N, dt, c
             f'"{times}","{subgraphs}","{left}"')
 
 
+def rhc_subgraphs(bits, ids):
+    """The `subgraphs` field of a round's CSV row from the round's neighbourhood masks: bits (k,) one 64-bit word per agent, or
+    (k, n_words) -- member q is bit q % 64 of word q // 64 (a word may come as a signed integer: bit 63 is its sign).  Per agent
+    the sorted ids of its neighbourhood, its own id as a Python int and its neighbours as NumPy ints (quirk Q10), so that the
+    list prints as solve_distributed's graph prints inside solve_rhc's rows."""
+    bits = np.asarray(bits)
+    k = len(ids)
+    words = bits.reshape(k, -1)
+    out = []
+    for i in range(k):
+        w = [int(v) for v in words[i]]
+        out.append(sorted([ids[i]] + [np.int64(ids[q]) for q in range(k) if q != i and (w[q >> 6] >> (q & 63)) & 1]))
+    return out
+
+
 def solve_rhc(problem, x0, N, *args, centralized=True, n_d=2, step_size=1, J_converge=None, dist_converge=None,
               t_diverge=None, i_trial=None, verbose=False, **kwargs):
     """Receding-horizon loop around solve_centralized / solve_distributed (distributed.py:106-221); logs the
@@ -207,7 +222,7 @@ def solve_rhc(problem, x0, N, *args, centralized=True, n_d=2, step_size=1, J_con
 
 def solve_rhc_scenarios(problem, x0, N, radius, xf=None, U0=None, centralized=False, n_d=2, step_size=1,
                         J_converge=None, dist_converge=None, t_diverge=None, window=None, i_trial=None, rows=None, max_cluster=None,
-                        **kwargs):
+                        wide=False, **kwargs):
     """solve_rhc (distributed.py:106-221) for S Monte-Carlo scenarios of one k-agent problem in lock step: every
     receding-horizon round is ONE batched solve over the scenarios still running (solve_scenarios_distributed, or one
     ProblemBatch when centralized), with the reference's warm-start shift and stopping rules applied per scenario.
@@ -220,9 +235,18 @@ def solve_rhc_scenarios(problem, x0, N, radius, xf=None, U0=None, centralized=Fa
     (distributed.py:190-194,215-219: one per receding-horizon round and the closing one), in its format (rhc_log_row);
     i_trial: their trial numbers (a sequence of S, or one value).  The `times` field is wall-clock there and here: each
     agent is given its share of the round's batched solve.  kwargs: n_lqr_iter, tol, t_kill reach every solve.
-    Not built for teams of more than 64 agents (centralized or not): ValueError before any device work.
+    Without wide=True a team of more than 64 agents (centralized or not) is a ValueError before any device work.
     max_cluster=m (an integer 1 .. 64; None: no cap; the distributed branch): every round's solve_scenarios_distributed caps the
     neighbourhoods at their m nearest agents, and the rows' `subgraphs` field shows the capped neighbourhoods.
+    wide=True serves the DISTRIBUTED loop (centralized=False) of any lowerable team of 1 .. 256 agents: every round is
+    solve_scenarios_distributed on the wide front end (multi-word masks, max_cluster honoured), the warm-start shift, the stopping
+    rules, t_diverge, the rows and the returned tuples are the ones above, and the rows' `subgraphs` field is decoded from the
+    multi-word masks (rhc_subgraphs).  J_full of a team of more than 64 agents is one ProblemBatch.rollout_wide per executed
+    length; a smaller team keeps ProblemBatch.rollout, so that at k <= 64 wide=True returns the default route's arrays and rows
+    (the wall-clock `times` field apart).  x0, xf and U0 may be device tensors (they are not modified).  It is opt-in; with
+    centralized=True, ignore_ids or shard=, more than 256 agents, or more than 12 agents of the five-state family it is a
+    ValueError before any device work.  Not built: fp32, shard=, ignore_ids; the wide route as a default; a centralized branch
+    for such teams.
     Returns a list of S tuples (X_full, U_full, J_full, converged), what solve_rhc returns plus its `converged` flag."""
     import torch
     from .batch import ProblemBatch
@@ -231,10 +255,22 @@ def solve_rhc_scenarios(problem, x0, N, radius, xf=None, U0=None, centralized=Fa
     from .lowering import describe
     if (J_converge is None) == (dist_converge is None):
         raise ValueError("Must either specify a convergence cost or distance")
+    from . import _lib
+    if wide:      # refused before the problem is even described: nothing here touches the device
+        from .batch import ROUTES
+        k_w = problem.n_agents
+        if centralized:
+            raise ValueError("solve_rhc_scenarios: wide=True is the distributed loop (centralized=False) of a team of up to "
+                             f"{_lib.MAX_TEAM} agents; no centralized solve is built for such teams")
+        if kwargs.get("ignore_ids") or kwargs.get("shard") is not None:
+            raise ValueError("solve_rhc_scenarios: wide=True serves neither shard= nor ignore_ids")
+        if k_w > _lib.MAX_TEAM:
+            raise ValueError(f"solve_rhc_scenarios: wide=True serves teams of up to {_lib.MAX_TEAM} agents (this one has {k_w})")
+        if problem.dynamics.n_x // k_w == 5 and k_w > ROUTES["team"]["max_k_of_ns"][5]:
+            raise ValueError(f"solve_rhc_scenarios: wide=True serves the five-state family up to 12 agents, this one has k = {k_w}")
     d = describe(problem)
     k, dt = d["k"], d["dt"]
-    from . import _lib
-    if k > _lib.MAX_AGENTS:
+    if k > _lib.MAX_AGENTS and not wide:
         raise ValueError(f"solve_rhc_scenarios is not built for teams of more than {_lib.MAX_AGENTS} agents (this one has {k}): "
                          "solve_scenarios_distributed and solve_distributed serve them, round by round")
     if max_cluster is not None:
@@ -244,12 +280,19 @@ def solve_rhc_scenarios(problem, x0, N, radius, xf=None, U0=None, centralized=Fa
             raise ValueError("solve_rhc_scenarios: max_cluster caps the neighbourhoods of the distributed solve (centralized=False)")
     n_x, n_u = problem.dynamics.n_x, problem.dynamics.n_u
     n_s = n_x // k
-    x0 = np.asarray(x0, dtype=np.float64).reshape(-1, n_x)
+    on_device = lambda a: isinstance(a, torch.Tensor)      # inputs given as device tensors stay there (and stay the caller's)
+    x0 = to_dev(x0).reshape(-1, n_x) if on_device(x0) else np.asarray(x0, dtype=np.float64).reshape(-1, n_x)
     S = x0.shape[0]
-    xf_h = np.broadcast_to(d["xf"], (S, n_x)).copy() if xf is None else np.asarray(xf, dtype=np.float64).reshape(S, n_x)
-    U_h = np.stack([np.random.rand(N, n_u) * 0.01 for _ in range(S)]) if U0 is None else np.array(U0, dtype=np.float64)
+    if xf is None:
+        xf_h = np.broadcast_to(d["xf"], (S, n_x)).copy()
+    else:
+        xf_h = to_dev(xf).reshape(S, n_x) if on_device(xf) else np.asarray(xf, dtype=np.float64).reshape(S, n_x)
+    if U0 is None:
+        U_h = np.stack([np.random.rand(N, n_u) * 0.01 for _ in range(S)])
+    else:
+        U_h = to_dev(U0).clone() if on_device(U0) else np.array(U0, dtype=np.float64)
     solve_kw = solve_kwargs(kwargs, "solve_rhc_scenarios")
-    xf_d, U, xi = to_dev(xf_h), to_dev(U_h), to_dev(x0)
+    xf_d, U, xi = to_dev(xf_h), to_dev(U_h), to_dev(x0).clone()
     X = None                                       # first round: the graph is built from x0 alone (distributed.py:152)
     J = torch.full((S,), float("inf"), dtype=torch.float64, device=xi.device)
     t = [0] * S                                    # the reference's t: the int 0 until the first `t += step_size * dt`
@@ -288,7 +331,8 @@ def solve_rhc_scenarios(problem, x0, N, radius, xf=None, U0=None, centralized=Fa
         else:
             Xin = xi[ia][:, None, :] if X is None else X[ia]
             Xa, Ua, Ja, info = solve_scenarios_distributed(problem, Xin, U[ia], radius, xf=xf_d[ia], window=window, device_out=True,
-                                                           desc=d, max_cluster=max_cluster, **solve_kw)
+                                                           desc=d, max_cluster=max_cluster, **({"wide": True} if wide else {}),
+                                                           **solve_kw)
             bits = info["cluster_bits"]
         if X is None:
             X = torch.zeros((S, N + 1, n_x), dtype=torch.float64, device=xi.device)
@@ -308,9 +352,8 @@ def solve_rhc_scenarios(problem, x0, N, radius, xf=None, U0=None, centralized=Fa
             for j, s in enumerate(active):
                 if centralized:
                     subgraphs = [ids] * k                                    # solve_centralized: {id: (dt, ids)}
-                else:      # the agent's own id as a Python int, its neighbours as NumPy ints (quirk Q10, as the rows print them)
-                    subgraphs = [sorted([ids[i]] + [np.int64(ids[q]) for q in range(k) if q != i and (int(bits[j, i]) >> q) & 1])
-                                 for i in range(k)]
+                else:
+                    subgraphs = rhc_subgraphs(bits[j], ids)
                 last_fields[s] = ([share] * k, subgraphs, left_h[j].tolist())
                 row_log[s].append(rhc_log_row(model_name, k, trial_of[s], centralized, False, t[s], float(J_h[j]), N, dt,
                                               bool(converged[s]), ids, *last_fields[s]))
@@ -329,7 +372,7 @@ def solve_rhc_scenarios(problem, x0, N, radius, xf=None, U0=None, centralized=Fa
         if X_parts[s]:
             XU.append((torch.cat(X_parts[s]).cpu().numpy(), torch.cat(U_parts[s]).cpu().numpy()))
         else:
-            XU.append((x0[s].copy(), np.zeros((1, n_u))))
+            XU.append((x0[s].cpu().numpy() if on_device(x0) else x0[s].copy(), np.zeros((1, n_u))))
     J_full = np.zeros(S)
     by_len = {}
     for s in range(S):
@@ -337,7 +380,10 @@ def solve_rhc_scenarios(problem, x0, N, radius, xf=None, U0=None, centralized=Fa
     for L_exec, idx in by_len.items():
         pbl = ProblemBatch(d["model"], d["n_dims"], xf_h[idx], d["Q"], d["R"], d["Qf"], d["radius"], dt, L_exec,
                            w_ref=d["w_ref"], w_prox=d["w_prox"], B=len(idx))
-        _, Jl = pbl.rollout(x0[idx], np.stack([XU[s][1] for s in idx]))
+        if k > _lib.MAX_AGENTS:      # the full-team rollout of the wide entries (as solve_scenarios_distributed's own J_full)
+            Jl = pbl.rollout_wide(x0[idx], np.stack([XU[s][1] for s in idx]), trajectories=False)["J"]
+        else:
+            _, Jl = pbl.rollout(x0[idx], np.stack([XU[s][1] for s in idx]))
         J_full[idx] = Jl.cpu().numpy()
     out = []
     for s in range(S):

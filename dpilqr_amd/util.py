@@ -183,12 +183,25 @@ def perturbed_starts(x0, x_dims, n_samples, n_d=2, var=0.5, seed=None):
     return np.stack([perturb_state(x0, x_dims, n_d=n_d, var=var).reshape(-1) for _ in range(int(n_samples))])
 
 
-def random_setup_batch(seeds, n_agents, n_states, var, n_d=2, energy=None):
+def random_setup_batch(seeds, n_agents, n_states, var, n_d=2, energy=None, wide=False):
     """(x0, xf) device tensors (S, n_agents * n_states) of the scenarios np.random.seed(s); random_setup(n_agents, n_states,
     is_rotation=False, var=var, n_d=n_d, random=True, energy=energy) for s in range(seeds[0], seeds[0] + S) -- generated on
     the device, bit for bit what the host loop gives (dpilqr_random_setup).  seeds: (first seed, count) or a range.
-    Not built for teams of more than 64 agents (the generator keeps a team's draws in one thread's registers): ValueError."""
+    Without wide=True a team of more than 64 agents is a ValueError (that generator keeps a team's draws in one thread's private
+    memory).  wide=True serves 1 .. 256 agents through dpilqr_trial_inputs with no warm start (include/dpilqr_swarm_study.h: a
+    wavefront per scenario, the generator's state in LDS), the same bits where both serve."""
     from . import _lib
+    if wide:
+        if not 1 <= n_agents <= _lib.MAX_TEAM:
+            raise ValueError(f"random_setup_batch: {n_agents} agents -- wide=True serves teams of 1 .. {_lib.MAX_TEAM}")
+        from .device import empty, ptr, stream_handle
+        if isinstance(seeds, range) and seeds.step != 1:
+            raise ValueError("consecutive seeds only")
+        seed0, S = (seeds.start, len(seeds)) if isinstance(seeds, range) else (int(seeds[0]), int(seeds[1]))
+        x0 = empty((S, n_agents * n_states)); xf = empty((S, n_agents * n_states))
+        _lib.check(_lib.load().dpilqr_trial_inputs(S, seed0, None, n_agents, n_states, n_d, float(var), float(energy or 0.0), 0, 0, 0, 0.0,
+                                                   ptr(x0), ptr(xf), None, None, stream_handle()))
+        return x0, xf
     if n_agents > _lib.MAX_AGENTS:
         raise ValueError(f"random_setup_batch: {n_agents} agents -- the device generator is not built for teams of more than "
                          f"{_lib.MAX_AGENTS}; draw the scenarios on the host (util.random_setup)")

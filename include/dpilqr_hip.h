@@ -379,6 +379,7 @@ int32_t dpilqr_random_setup(int32_t S, int64_t seed0, int32_t k, int32_t n_s, in
 #include "dpilqr_swarm.h"
 #include "dpilqr_swarm_policy.h"
 #include "dpilqr_swarm_advance.h"
+#include "dpilqr_swarm_study.h"
 #include "dpilqr_order.h"
 #include "dpilqr_nearest.h"
 
