@@ -146,6 +146,14 @@ SWARM_STUDY_SIGNATURES = {
 }
 TRIAL_INPUTS_LDS = 37888     # DPILQR_TRIAL_INPUTS_LDS
 
+# ... and of include/dpilqr_separated_setup.h: drawn positions pushed apart to a minimum separation -- S, k, n_s, n_d, rel_dist,
+# energy, max_iter, x0, xf, n_iter, stream
+SEPARATED_SIGNATURES = {
+    "dpilqr_setup_separate": (i32, [i32, i32, i32, i32, C.c_double, C.c_double, i32, vp, vp, vp, vp]),
+}
+SETUP_SEPARATE_MAX_ITER = 4096     # DPILQR_SETUP_SEPARATE_MAX_ITER
+SETUP_SEPARATE_LDS = 8232          # DPILQR_SETUP_SEPARATE_LDS
+
 MAX_AGENTS = 64          # DPILQR_MAX_AGENTS: agents of a sub-problem (cluster), and of a problem on the one-word entries
 MAX_TEAM = 256           # DPILQR_MAX_TEAM: agents of a problem on the wide entries (include/dpilqr_swarm.h)
 
@@ -173,7 +181,7 @@ def load():
                               "(hipcc --offload-arch=gfx950).  dpilqr_amd has no CPU fallback.")
         lib = C.CDLL(str(LIB_PATH))
         for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **SWARM_SIGNATURES, **SWARM_POLICY_SIGNATURES, **SWARM_ADVANCE_SIGNATURES,
-                                   **ORDER_SIGNATURES, **NEAREST_SIGNATURES, **SWARM_STUDY_SIGNATURES}.items():
+                                   **ORDER_SIGNATURES, **NEAREST_SIGNATURES, **SWARM_STUDY_SIGNATURES, **SEPARATED_SIGNATURES}.items():
             fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -32,7 +32,7 @@ from .cost import GameCost, ProximityCost, ReferenceCost
 from .distributed import solve_rhc_scenarios
 from .dynamics import DoubleIntDynamics4D, MultiDynamicalModel, QuadcopterDynamics6D, UnicycleDynamics4D
 from .problem import ilqrProblem
-from .util import random_setup, split_agents_gen
+from .util import random_setup, separate_setups, split_agents_gen
 
 HEADER = "dynamics,n_agents,trial,centralized,last,t,J,horizon,dt,converged,ids,times,subgraphs,dist_left"   # analysis.py:120-123
 STEP_SIZE = 3                                                                                                # analysis.py:43
@@ -44,27 +44,35 @@ def seed_of(model, n_agents, i_trial, seed0=0):
     return int(seed0) + 100003 * MODELS.index(model) + 1009 * int(n_agents) + int(i_trial)
 
 
-def trial_inputs(n_agents, n_states, n_u, N, energy, n_d, seed):
+def trial_inputs(n_agents, n_states, n_u, N, energy, n_d, seed, separated=False, rel_dist=None):
     """What one trial of multi_agent_run draws, in the order the reference draws it: (x0, xf) from random_setup
-    (analysis.py:45-54), then the warm start of the centralized and of the distributed solve_rhc (distributed.py:152)."""
+    (analysis.py:45-54), then the warm start of the centralized and of the distributed solve_rhc (distributed.py:152).
+    separated=True: random_setup's random=False with the same arguments -- every pair of starts and of goals farther apart than
+    rel_dist (None: n_agents, what the study passes) before the energy is normalised.  The push draws nothing: the warm starts are
+    those of separated=False."""
     np.random.seed(seed)
-    x0, xf = random_setup(n_agents, n_states, is_rotation=False, rel_dist=n_agents, var=n_agents / 2, n_d=n_d, random=True,
-                          energy=energy)
+    x0, xf = random_setup(n_agents, n_states, is_rotation=False, rel_dist=n_agents if rel_dist is None else rel_dist, var=n_agents / 2,
+                          n_d=n_d, random=not separated, energy=energy)
     U_c = np.random.rand(N, n_u) * 0.01
     U_d = np.random.rand(N, n_u) * 0.01
     return x0, xf, U_c, U_d
 
 
-def trial_inputs_batch(n_agents, n_states, n_u, N, energy, n_d, seeds):
+def trial_inputs_batch(n_agents, n_states, n_u, N, energy, n_d, seeds, separated=False, rel_dist=None, max_iter=256):
     """trial_inputs for the S trials seeded `seeds`, drawn on the device (dpilqr_trial_inputs, include/dpilqr_swarm_study.h): device
     tensors x0, xf (S, n_agents * n_states) and U_c, U_d (S, N, n_u), bit for bit trial_inputs' four arrays of every seed, for
     teams of 1 .. 256 agents -- var = n_agents / 2 and the warm starts scaled by 0.01 as there.  seeds: any sequence of integers
-    of [0, 2^32); a consecutive run is passed as its first seed, anything else as a device array."""
+    of [0, 2^32); a consecutive run is passed as its first seed, anything else as a device array.
+    separated=True: trial_inputs(separated=True)'s arrays for teams of 2 .. 256 agents -- the raw draws (energy 0), then
+    dpilqr_setup_separate (include/dpilqr_separated_setup.h) with rel_dist (None: n_agents); the round counts are read back once and
+    a set that did not separate within max_iter rounds is a ValueError naming its seed (util.separate_setups)."""
     import torch
     from . import _lib
     from .device import empty, ptr, stream_handle, to_dev
     seeds = [int(s) for s in seeds]
     S = len(seeds)
+    if separated and n_agents == 1:
+        raise ValueError("Can't compute pairwise distance for one agent.")
     if not 1 <= n_agents <= _lib.MAX_TEAM:
         raise ValueError(f"trial_inputs_batch: {n_agents} agents -- the device generator serves teams of 1 .. {_lib.MAX_TEAM}")
     if any(not 0 <= s < 2 ** 32 for s in seeds):
@@ -74,8 +82,11 @@ def trial_inputs_batch(n_agents, n_states, n_u, N, energy, n_d, seeds):
     consecutive = all(b == a + 1 for a, b in zip(seeds, seeds[1:]))
     seeds_d = None if consecutive else to_dev(torch.tensor(seeds, dtype=torch.int64), torch.int64)
     _lib.check(_lib.load().dpilqr_trial_inputs(S, seeds[0] if S and consecutive else 0, ptr(seeds_d), n_agents, n_states, n_d,
-                                               float(n_agents / 2), float(energy or 0.0), 2, N, n_u, 0.01, ptr(x0), ptr(xf), ptr(U_c),
-                                               ptr(U_d), stream_handle()))
+                                               float(n_agents / 2), 0.0 if separated else float(energy or 0.0), 2, N, n_u, 0.01, ptr(x0),
+                                               ptr(xf), ptr(U_c), ptr(U_d), stream_handle()))
+    if separated:
+        separate_setups(x0, xf, seeds, n_agents, n_states, n_d, float(n_agents if rel_dist is None else rel_dist), energy, max_iter,
+                        "trial_inputs_batch")
     return x0, xf, U_c, U_d
 
 
@@ -103,7 +114,7 @@ def build_problem(model, n_agents, dt, radius, xf, n_d):
 
 
 def multi_agent_run(model, x_dims, dt, N, radius, energy=10.0, n_d=2, trials=(0,), seed0=0, emit=logging.info, window=None,
-                    branches=(True, False), wide=False, max_cluster=None, device_inputs=False, **kwargs):
+                    branches=(True, False), wide=False, max_cluster=None, device_inputs=False, separated=False, **kwargs):
     """multi_agent_run (analysis.py:35-107) for all `trials` of one (model, team size) at once: both branches, every
     receding-horizon round of every trial one batched solve.  kwargs as the reference passes them: t_kill, dist_converge,
     t_diverge (i_trial is replaced by `trials`; energy is consumed here).  Emits the rows in the reference's order and
@@ -115,7 +126,9 @@ def multi_agent_run(model, x_dims, dt, N, radius, energy=10.0, n_d=2, trials=(0,
     wide, max_cluster reach the distributed branch's solve_rhc_scenarios: with wide=True a swarm of up to 256 agents is studied,
     distributed only (no centralized solve is built above n_x = 240: wide=True with True in branches is a ValueError).
     device_inputs=True draws the trials' inputs on the device (trial_inputs_batch: the same bits) and hands the device tensors
-    to the loops; they never come to the host."""
+    to the loops; they never come to the host.
+    separated=True draws every trial with trial_inputs(separated=True) -- random_setup's random=False, pairs of starts and of goals
+    farther apart than rel_dist = n_agents before normalisation -- on either input path (the same bits)."""
     if not len(set(x_dims)) == 1:
         raise ValueError("Dynamics dimensions must be consistent")
     branches = tuple(bool(b) for b in branches)
@@ -130,11 +143,11 @@ def multi_agent_run(model, x_dims, dt, N, radius, energy=10.0, n_d=2, trials=(0,
     n_u = n_agents * model(-1).n_u
     seeds = [seed_of(model, n_agents, i, seed0) for i in trials]
     if device_inputs:
-        x0, xf, U_c, U_d = trial_inputs_batch(n_agents, n_states, n_u, N, energy, n_d, seeds)
+        x0, xf, U_c, U_d = trial_inputs_batch(n_agents, n_states, n_u, N, energy, n_d, seeds, separated=separated)
         warm = {True: U_c, False: U_d}
         xf_first = xf[0].cpu().numpy()
     else:
-        drawn = [trial_inputs(n_agents, n_states, n_u, N, energy, n_d, seed) for seed in seeds]
+        drawn = [trial_inputs(n_agents, n_states, n_u, N, energy, n_d, seed, separated=separated) for seed in seeds]
         x0 = np.stack([d[0].ravel() for d in drawn]); xf = np.stack([d[1].ravel() for d in drawn])
         warm = {centralized: np.stack([d[col] for d in drawn]) for centralized, col in ((True, 2), (False, 3)) if centralized in branches}
         xf_first = xf[0]
@@ -185,10 +198,10 @@ def setup_logger(limit_solve_time, log_file=None):
 
 def monte_carlo_analysis(limit_solve_time=False, n_trials=2, n_agents_iter=(3, 4, 5, 6, 7), models=MODELS, dt=0.1, N=50,
                          energy=10.0, radius=0.50, seed0=0, log_file=None, emit=None, window=None, branches=(True, False), wide=False,
-                         max_cluster=None, device_inputs=False):
+                         max_cluster=None, device_inputs=False, separated=False):
     """monte_carlo_analysis (analysis.py:126-174): the same loops, constants and stopping rules; the innermost loop (the
     trials) is the batch.  n_trials may be thousands -- that is what the batched path is for.
-    branches, wide, max_cluster, device_inputs: multi_agent_run's, passed through -- branches=(False,), wide=True studies
+    branches, wide, max_cluster, device_inputs, separated: multi_agent_run's, passed through -- branches=(False,), wide=True studies
     swarms of up to 256 agents, distributed only.  energy may be a callable of n_agents: the reference's fixed 10.0 puts 256
     agents within one radius of each other, a swarm needs an energy that grows with the team."""
     if emit is None:
@@ -208,5 +221,5 @@ def monte_carlo_analysis(limit_solve_time=False, n_trials=2, n_agents_iter=(3, 4
             results[(model.__name__, n_agents)] = multi_agent_run(
                 model, x_dims, dt, N, radius, n_d=n_d, t_kill=t_kill, dist_converge=0.1, t_diverge=t_diverge,
                 energy=energy(n_agents) if callable(energy) else energy, trials=range(n_trials), seed0=seed0, emit=emit, window=window,
-                branches=branches, wide=wide, max_cluster=max_cluster, device_inputs=device_inputs, verbose=False)
+                branches=branches, wide=wide, max_cluster=max_cluster, device_inputs=device_inputs, separated=separated, verbose=False)
     return results

@@ -134,6 +134,37 @@ def randomize_locs(n_pts, random=False, rel_dist=3.0, var=3.0, n_d=2):
         x[close] += push * (x[close] - centre)
 
 
+def separate_locs(x, rel_dist, max_iter=None):
+    """The loop of randomize_locs(random=False) on a (k, n_d) array that is already drawn, stated point by point as the device
+    computes it (include/dpilqr_separated_setup.h): per round the centre, the distances over the first two coordinates, a flag per
+    point with another point within rel_dist, and every flagged point pushed once, x + 0.1 k (x - centre), all from the old
+    positions.  Returns (x, rounds): a copy, and the number of rounds, the last one -- which finds no flag -- included.  With
+    max_iter, a set that still has a flagged point in round max_iter comes back as it stands after that round's push, with
+    rounds = -1.  One point raises like the reference's compute_pairwise_distance."""
+    x = np.array(x, dtype=np.float64)
+    k, n_d = x.shape
+    if k == 1:
+        raise ValueError("Can't compute pairwise distance for one agent.")
+    push = 0.1 * k
+    rounds = 0
+    while True:
+        rounds += 1
+        centre = x.mean(axis=0)
+        with np.errstate(invalid="ignore", over="ignore"):
+            d = x[:, None, :2] - x[None, :, :2]
+            q = d[..., 0] * d[..., 0]
+            if d.shape[2] == 2:
+                q = q + d[..., 1] * d[..., 1]
+            close = np.sqrt(q) <= rel_dist
+            np.fill_diagonal(close, False)
+            flag = close.any(axis=1)
+            if not flag.any():
+                return x, rounds
+            x[flag] = x[flag] + push * (x[flag] - centre)
+        if max_iter is not None and rounds >= max_iter:
+            return x, -1
+
+
 def compute_energy(x, x_dims, n_d=2):
     return np.linalg.norm(x[pos_mask(x_dims, n_d)].reshape(-1, n_d), axis=1).sum()
 
@@ -183,14 +214,59 @@ def perturbed_starts(x0, x_dims, n_samples, n_d=2, var=0.5, seed=None):
     return np.stack([perturb_state(x0, x_dims, n_d=n_d, var=var).reshape(-1) for _ in range(int(n_samples))])
 
 
-def random_setup_batch(seeds, n_agents, n_states, var, n_d=2, energy=None, wide=False):
+def separate_setups(x0, xf, seeds, n_agents, n_states, n_d, rel_dist, energy, max_iter=256, who="separate_setups"):
+    """dpilqr_setup_separate (include/dpilqr_separated_setup.h) on device tensors x0, xf (S, n_agents * n_states) of RAW draws, in
+    place: the position columns become those of random_setup(..., rel_dist=rel_dist, random=False, energy=energy).  The (S, 2)
+    round counts (starts, goals) are read back once and returned; a set that did not separate within max_iter rounds is a
+    ValueError naming its seed (seeds: the S seeds, for that message) and set."""
+    from . import _lib
+    if n_agents == 1:
+        raise ValueError("Can't compute pairwise distance for one agent.")
+    if not 2 <= n_agents <= _lib.MAX_TEAM:
+        raise ValueError(f"{who}: {n_agents} agents -- separated=True serves teams of 2 .. {_lib.MAX_TEAM}")
+    import torch
+    from .device import empty, ptr, stream_handle
+    S = x0.shape[0]
+    n_iter = empty((S, 2), torch.int32)
+    _lib.check(_lib.load().dpilqr_setup_separate(S, n_agents, n_states, n_d, float(rel_dist), float(energy or 0.0), int(max_iter), ptr(x0),
+                                                 ptr(xf), ptr(n_iter), stream_handle()))
+    rounds = n_iter.cpu().numpy()
+    if (rounds < 0).any():
+        stuck = ", ".join(f"seed {int(seeds[s])} ({'starts' if w == 0 else 'goals'})" for s, w in np.argwhere(rounds < 0))
+        raise ValueError(f"{who}: not separated to rel_dist={rel_dist} within max_iter={max_iter} rounds: {stuck}")
+    return rounds
+
+
+def random_setup_batch(seeds, n_agents, n_states, var, n_d=2, energy=None, wide=False, separated=False, rel_dist=3.0, max_iter=256,
+                       return_rounds=False):
     """(x0, xf) device tensors (S, n_agents * n_states) of the scenarios np.random.seed(s); random_setup(n_agents, n_states,
     is_rotation=False, var=var, n_d=n_d, random=True, energy=energy) for s in range(seeds[0], seeds[0] + S) -- generated on
     the device, bit for bit what the host loop gives (dpilqr_random_setup).  seeds: (first seed, count) or a range.
     Without wide=True a team of more than 64 agents is a ValueError (that generator keeps a team's draws in one thread's private
     memory).  wide=True serves 1 .. 256 agents through dpilqr_trial_inputs with no warm start (include/dpilqr_swarm_study.h: a
-    wavefront per scenario, the generator's state in LDS), the same bits where both serve."""
+    wavefront per scenario, the generator's state in LDS), the same bits where both serve.
+    separated=True: random_setup(..., rel_dist=rel_dist, random=False, ...) instead -- every pair of starts and every pair of goals
+    farther apart than rel_dist before the energy is normalised -- for 2 .. 256 agents whatever `wide` is: the raw draws of
+    dpilqr_trial_inputs, then dpilqr_setup_separate (include/dpilqr_separated_setup.h).  The round counts are read back once; a
+    set that did not separate within max_iter rounds is a ValueError naming its seed.  return_rounds=True (separated only) also
+    returns the (S, 2) counts of the start and goal sets."""
     from . import _lib
+    if separated:
+        if n_agents == 1:
+            raise ValueError("Can't compute pairwise distance for one agent.")
+        if not 2 <= n_agents <= _lib.MAX_TEAM:
+            raise ValueError(f"random_setup_batch: {n_agents} agents -- separated=True serves teams of 2 .. {_lib.MAX_TEAM}")
+        from .device import empty, ptr, stream_handle
+        if isinstance(seeds, range) and seeds.step != 1:
+            raise ValueError("consecutive seeds only")
+        seed0, S = (seeds.start, len(seeds)) if isinstance(seeds, range) else (int(seeds[0]), int(seeds[1]))
+        x0 = empty((S, n_agents * n_states)); xf = empty((S, n_agents * n_states))
+        _lib.check(_lib.load().dpilqr_trial_inputs(S, seed0, None, n_agents, n_states, n_d, float(var), 0.0, 0, 0, 0, 0.0, ptr(x0), ptr(xf),
+                                                   None, None, stream_handle()))
+        rounds = separate_setups(x0, xf, range(seed0, seed0 + S), n_agents, n_states, n_d, rel_dist, energy, max_iter, "random_setup_batch")
+        return (x0, xf, rounds) if return_rounds else (x0, xf)
+    if return_rounds:
+        raise ValueError("random_setup_batch: return_rounds=True goes with separated=True")
     if wide:
         if not 1 <= n_agents <= _lib.MAX_TEAM:
             raise ValueError(f"random_setup_batch: {n_agents} agents -- wide=True serves teams of 1 .. {_lib.MAX_TEAM}")

@@ -382,6 +382,7 @@ int32_t dpilqr_random_setup(int32_t S, int64_t seed0, int32_t k, int32_t n_s, in
 #include "dpilqr_swarm_study.h"
 #include "dpilqr_order.h"
 #include "dpilqr_nearest.h"
+#include "dpilqr_separated_setup.h"
 
 #ifdef __cplusplus
 }

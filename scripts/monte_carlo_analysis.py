@@ -27,12 +27,16 @@ def main():
                     help="teams of up to 256 agents: the distributed loop alone on the wide route, the inputs drawn on the device")
     ap.add_argument("--max-cluster", type=int, default=None, help="cap every neighbourhood at its m nearest agents")
     ap.add_argument("--energy-per-agent", type=float, default=None, help="energy = this times the team size (default: the reference's 10.0)")
+    ap.add_argument("--separated", action="store_true",
+                    help="random_setup's random=False: starts and goals pushed apart to rel_dist = the team size before normalisation")
     a = ap.parse_args()
     from dpilqr_amd import analysis
     models = analysis.MODELS if a.models is None else tuple(m for m in analysis.MODELS if m.__name__ in a.models)
     extra = dict(branches=(False,), wide=True, device_inputs=True) if a.swarm else {}
     if a.max_cluster is not None:
         extra["max_cluster"] = a.max_cluster
+    if a.separated:
+        extra["separated"] = True
     if a.energy_per_agent is not None:
         extra["energy"] = lambda n_agents: a.energy_per_agent * n_agents
     t0 = time.perf_counter()
